@@ -7,6 +7,14 @@ step   : one pass of the fused frame kernel over one batch of --nblk blocks
          (default 2048 x 65536 int16 = 256 MiB, resident in HBM before timing)
 
   python bench.py [--gpus N --steps K --warmup W] [--d 0] [--mode single|channels]
+                  [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line (headline value,
+ms_per_step, the HBM roofline of the timed kernel).  --dump-outputs DIR also writes what the
+last timed step computed as DIR/<name>.npy.  --full adds every other leg, each a run of its
+own after the timed steps: the C3/C4 sweep, the segment self-check, the CPU baselines with the
+IQ error against the f64 oracle, and the C5 leg (and, at N > 1 or --streams > 1, the collective
+and the single-stream kernel timed alone).
 
 N > 1 (launched by torch.distributed.run, one rank per GPU):
   single   : weak scaling — each rank owns its own time segment of the stream
@@ -59,6 +67,39 @@ def make_input(torch, nblk: int, seed: int, device, first_block: int = 0) -> "to
     out[t < 0] = 0                                        # before the stream start: zero history
     del x, t
     return out
+
+
+DUMP_BUDGET_BYTES = 48 << 20   # per run, all ranks together (float32 on disk)
+DUMP_CHUNK = 16384             # elements: a sampled dump keeps whole chunks of this many
+DUMP_SEED = 0x5DDC
+
+
+def dump_output(torch, out_dir: str, name: str, t, budget_bytes: int) -> dict:
+    """Write the device tensor t (the timed path's output buffer after the last timed step) as
+    out_dir/name.npy, float32 (CF32 as interleaved re, im; CS16's int16 is exact in float32).
+    An output larger than the budget is sampled: a fixed, seeded choice of DUMP_CHUNK-element
+    chunks of the flattened buffer (always its first and last chunk), in ascending order, so
+    two runs with the same arguments write the same elements."""
+    os.makedirs(out_dir, exist_ok=True)
+    flat = t.reshape(-1)
+    n = flat.numel()
+    info = {"file": name + ".npy", "dtype": "float32", "elements_total": n, "sampled": False}
+    if n * 4 > budget_bytes:
+        nchunks = (n + DUMP_CHUNK - 1) // DUMP_CHUNK
+        keep = max(2, budget_bytes // (4 * DUMP_CHUNK))
+        rng = np.random.default_rng(DUMP_SEED)
+        mid = rng.choice(np.arange(1, nchunks - 1), size=keep - 2, replace=False)
+        chunks = np.sort(np.concatenate([[0, nchunks - 1], mid])).astype(np.int64)
+        idx = (torch.from_numpy(chunks).to(flat.device)[:, None] * DUMP_CHUNK
+               + torch.arange(DUMP_CHUNK, device=flat.device)[None, :]).reshape(-1)
+        idx = idx[idx < n]
+        flat = flat[idx]
+        info.update({"sampled": True, "chunk_elements": DUMP_CHUNK, "chunks_kept": int(chunks.size),
+                     "chunks_total": int(nchunks), "seed": DUMP_SEED})
+    a = flat.to(torch.float32).cpu().numpy()
+    np.save(os.path.join(out_dir, name + ".npy"), a)
+    info["elements_written"] = int(a.size)
+    return info
 
 
 def segment_check(torch, ddc, d: int, nblk: int, rank: int, dev, stream, d_out) -> dict:
@@ -516,15 +557,22 @@ def main() -> None:
     ap.add_argument("--bcast", choices=["sag", "bcast"], default="sag",
                     help="C5 input broadcast for N > 1: scatter + all-gather over all links (sag) or one "
                          "broadcast collective (shard.broadcast_samples)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg: the C3/C4 sweep, the segment "
+                         "self-check, the CPU baselines and the IQ error against the f64 oracle, the C5 leg "
+                         "(--no-sweep, --no-cpu-baseline and --no-c5 each drop one of them again)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the output of the last timed step as DIR/<name>.npy "
+                         "(float32; a fixed seeded sample of chunks when it is larger than 48 MiB)")
     ap.add_argument("--no-c5", action="store_true",
-                    help="skip the same-run C5 leg (1024 channels at d = 4, sharded over the ranks)")
+                    help="with --full: skip the same-run C5 leg (1024 channels at d = 4, sharded over the ranks)")
     ap.add_argument("--c5-nblk", type=int, default=256, help="C5 leg: blocks of 65536 per batch")
     ap.add_argument("--c5-steps", type=int, default=20, help="C5 leg: timed batches")
     ap.add_argument("--c5-timeout", type=float, default=120.0, help="C5 leg watchdog, seconds")
     ap.add_argument("--cpu-budget", type=float, default=10.0, help="seconds of CPU-baseline work")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU-baseline legs")
     ap.add_argument("--no-sweep", action="store_true",
-                    help="skip the same-run C3 decim sweep / C4 VHF lines (BASELINE.md §3)")
+                    help="with --full: skip the same-run C3 decim sweep / C4 VHF lines (BASELINE.md §3)")
     ap.add_argument("--cs16", type=float, default=0.0,
                     help="CS16 output with this scale (int16 = rint(x * scale)); 0 = CF32")
     ap.add_argument("--fine-tune", type=float, default=0.0,
@@ -661,10 +709,18 @@ def main() -> None:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     wall, kern_ms = t.tolist()
 
+    # what a caller of the timed path holds after its last timed step, before any other leg
+    # launches into the same buffers
+    dumped = None
+    if args.dump_outputs:
+        last = pouts[(args.steps - 1) % nstreams] if args.mode == "single" else d_out
+        dumped = dump_output(torch, args.dump_outputs, "iq" if world == 1 else f"iq_rank{rank}", last,
+                             DUMP_BUDGET_BYTES // world)
+
     # pipelined batches: the kernel's own launch duration (roofline, rocprof) from the same steps
     # launched back to back on one stream, timed the same way (max over ranks)
     single = None
-    if nstreams > 1:
+    if nstreams > 1 and args.full:
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
@@ -694,14 +750,14 @@ def main() -> None:
     # N > 1 channels: the collective and the compute, each timed alone (max over ranks), so the
     # line shows which of the two bounds the pipelined step
     bcast_info = None
-    if args.mode == "channels" and world > 1:
+    if args.full and args.mode == "channels" and world > 1:
         bcast_info = ch.broadcast_and_compute_alone(backend)
 
 
     # BASELINE.md §3 / SURVEY §8(d) C3 + C4 in the same run, while the clocks are at their
     # steady state: GPU rate and roofline per config (the headline value stays the d=0 line)
     sweep = []
-    if rank == 0 and world == 1 and args.mode == "single" and not args.no_sweep and not (args.cs16 or args.fine_tune):
+    if args.full and rank == 0 and world == 1 and args.mode == "single" and not args.no_sweep and not (args.cs16 or args.fine_tune):
         for dd, lsb, rnd, name in [(0, 0, 0, "C3 decim 2"), (1, 0, 0, "C3 decim 4"), (2, 0, 0, "C3 decim 8"),
                                    (3, 0, 0, "C3 decim 16"), (4, 0, 0, "C3 decim 32"),
                                    (1, 1, 1, "C4 VHF decim 4, sideband invert, rand")]:
@@ -731,7 +787,7 @@ def main() -> None:
     # After the sweep: its host round trips idle the GPU, and the sweep's first config (d = 0) would
     # then run on a clock still ramping back up
     seg_check = None
-    if args.mode == "single" and not (args.cs16 or args.fine_tune):
+    if args.full and args.mode == "single" and not (args.cs16 or args.fine_tune):
         seg_check = segment_check(torch, ddc, d, nblk, rank, dev, stream, d_out)
         if world > 1:
             tt = torch.tensor([seg_check["max_rel_err"], 0.0 if seg_check["bit_identical"] else 1.0],
@@ -749,6 +805,7 @@ def main() -> None:
     result = {
         "metric": "input MSamples/s at decim=2 + achieved % HBM roofline, 1 GPU; IQ max-rel-err",
         "value": value, "unit": "input MSamples/s", "n_gpus": world, "steps": args.steps,
+        "full": args.full,
         "warmup": args.warmup, "warmup_ms": warmup_ms, "warmup_extra_steps": extra,
         "ms_per_step": wall * 1e3 / args.steps, "higher_is_better": True,
         "scaling": "weak" if args.mode == "single" else "strong",
@@ -774,13 +831,19 @@ def main() -> None:
 
     if single:
         result["pipelining"] = single
+    elif nstreams > 1:
+        result["pipelining"] = {"streams": nstreams,
+                                "note": "roofline.kernel_ms_per_launch is the pipelined steps' HIP-event time per "
+                                        "step; --full times the same steps on one stream for the kernel's own"}
+    if dumped:
+        result["dump_outputs"] = dumped
     if bcast_info:
         result["broadcast"] = bcast_info
     if args.mode == "channels" and world > 1:
         result["broadcast_check"] = ch.bcast_check
     if seg_check:
         result["segment_check"] = seg_check
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         ns = 16
         sample = d_in[: HALF + ns * BLOCK].cpu().numpy()
         if args.mode == "single":
@@ -822,7 +885,7 @@ def main() -> None:
     # Reported beside the headline, which it does not change.  It runs after the headline is
     # complete, under a watchdog: should its collectives stall, rank 0 still prints the line
     # (with the C5 error) and every rank exits.
-    if args.mode == "single" and not (args.no_c5 or args.cs16 or args.fine_tune):
+    if args.full and args.mode == "single" and not (args.no_c5 or args.cs16 or args.fine_tune):
         import threading
 
         def stalled():

@@ -8,7 +8,7 @@
 set -o pipefail
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd "$R"; TAG=${1:-round}; O=$R/gpurun_out/$TAG; mkdir -p $O
-BENCH="bench.py --gpus 1 --steps 20 --warmup 5"
+BENCH="bench.py --gpus 1 --steps 20 --warmup 5 --full"
 crashed() { case "$1" in 124|134|137|139) return 0;; *) return 1;; esac; }
 if [ -z "$SKIP_TESTS" ]; then
   timeout -k 10 600 python -u -m pytest tests -m gpu -x -q -rfE --timeout 120 --timeout-method thread > $O/pytest_gpu.log 2>&1

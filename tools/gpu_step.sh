@@ -32,10 +32,10 @@ while [ $# -gt 0 ]; do
       timeout -k 10 300 python -u tools/fs_stamps.py $2 >> $O/stamps.log 2>&1
       rc=$?; echo "stamps rc=$rc" >> $O/stamps.log; crashed $rc && exit $rc; shift ;;
     --bench)
-      timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.log 2>&1
+      timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench.log 2>&1
       rc=$?; echo "bench rc=$rc" >> $O/bench.log; crashed $rc && exit $rc ;;
     --prof)
-      (cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o run -- python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 > $O/trace.log 2>&1)
+      (cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o run -- python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/trace.log 2>&1)
       rc=$?; echo "prof rc=$rc" >> $O/trace.log; crashed $rc && exit $rc ;;
   esac
   shift
