@@ -45,6 +45,8 @@ SIGNATURES = {
     "sddc_ddc_set_freq_offset": (_F, [_P, _F]),
     "sddc_ddc_reset": (_I, [_P]),
     "sddc_ddc_set_fine_tune": (_I, [_P, _F]),
+    "sddc_ddc_set_channel_fine_tune": (_I, [_P, _P, _I]),
+    "sddc_ddc_channel_tuning": (_I, [_F, _I, ctypes.POINTER(_I), ctypes.POINTER(_F)]),
     "sddc_ddc_set_output_format": (_I, [_P, _I, _F]),
     "sddc_ddc_output_samples": (_SZ, [_I, _I]),
     "sddc_ddc_process_device": (_I, [_P, _P, _I, _P, _P]),

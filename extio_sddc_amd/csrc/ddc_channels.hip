@@ -92,12 +92,30 @@ __device__ __forceinline__ float2 split2(float2 zk, float2 zc, float2 wk)
 // goes into a window xw with N/2 zeros either side, so every channel bin, in band or not, reads
 // xw[bin - lo + N/2] without a range test; the per-channel slices reuse the transform buffer
 // (3 workgroups per CU).  Otherwise the split is done in place over all 4096 bins.
-template <int D, bool RAND, bool CS16, bool COMPACT, bool STAGE_OK>
+// Per-channel fine-tune NCO (ddc_kernels.h ChNco): channel c's tables and whether it mixes.
+struct ChMix {
+    NcoArgs na;
+    bool on;
+};
+__device__ __forceinline__ ChMix ch_mix_of(const ChNco &cn, int c)
+{
+    return ChMix{NcoArgs{cn.starts + (size_t)c * (size_t)cn.nb * 4, cn.trig + c * 32}, cn.fc[c] != 0.f};
+}
+// o: the sample's position in the channel's stream relative to the run; an fc = 0 channel keeps v
+__device__ __forceinline__ float2 ch_mix(float2 v, const ChMix &m, int o)
+{
+    const float2 w = nco_mix(v, m.na, o);
+    return m.on ? w : v;
+}
+
+// NCO: the per-channel fine-tune NCO in the output stage (after flip, before the CS16 pack, as
+// emit_frame); instantiated from the NCO launch path only.
+template <int D, bool RAND, bool CS16, bool COMPACT, bool STAGE_OK, bool NCO = false>
 __global__ __launch_bounds__(NT, 2) void r2iq_channels_v2_kernel(
     const int *__restrict__ in32, void *__restrict__ out, size_t stride, int nframes,
     const int *__restrict__ tunebins, int nch, const float2 *__restrict__ tw_p1,
     const float2 *__restrict__ rec_f, const float2 *__restrict__ post8192, const float2 *__restrict__ hsel,
-    OutArgs oa, const int2 *__restrict__ windows, float2 *__restrict__ scratch)
+    OutArgs oa, const int2 *__restrict__ windows, float2 *__restrict__ scratch, ChNco cn)
 {
     constexpr int N = HALF >> D;
     static_assert(N <= 256 && N >= 64, "channels v2 covers d = 4..6");
@@ -302,11 +320,24 @@ __global__ __launch_bounds__(NT, 2) void r2iq_channels_v2_kernel(
                         const int swc = (((g & ~(CW - 1)) + cl) * TPC) & 12;
                         const float2 *src = slices + cl * N;
                         const int n = n0 + PER * pc;
-                        const float4 p0 = *reinterpret_cast<const float4 *>(src + (n ^ swc));
+                        float4 p0 = *reinterpret_cast<const float4 *>(src + (n ^ swc));
+                        const int orun = blk * 8 * N + o0 + (n - n0);   // position in the channel's run
+                        ChMix cm;
+                        if constexpr (NCO) {
+                            cm = ch_mix_of(cn, c);   // c < cend <= nch
+                            const float2 a = ch_mix(make_float2(p0.x, p0.y), cm, orun);
+                            const float2 b = ch_mix(make_float2(p0.z, p0.w), cm, orun + 1);
+                            p0 = make_float4(a.x, a.y, b.x, b.y);
+                        }
                         char *ob = static_cast<char *>(out) +
                                    ((size_t)c * stride + (size_t)blk * 8 * N + o0 + (n - n0)) * out_bytes<CS16>();
                         if constexpr (CS16) {
-                            const float4 p1 = *reinterpret_cast<const float4 *>(src + ((n + 2) ^ swc));
+                            float4 p1 = *reinterpret_cast<const float4 *>(src + ((n + 2) ^ swc));
+                            if constexpr (NCO) {
+                                const float2 a = ch_mix(make_float2(p1.x, p1.y), cm, orun + 2);
+                                const float2 b = ch_mix(make_float2(p1.z, p1.w), cm, orun + 3);
+                                p1 = make_float4(a.x, a.y, b.x, b.y);
+                            }
                             u32x4 v;
                             v.x = cs16_pack(make_float2(p0.x, p0.y), oa.scale);
                             v.y = cs16_pack(make_float2(p0.z, p0.w), oa.scale);
@@ -326,7 +357,10 @@ __global__ __launch_bounds__(NT, 2) void r2iq_channels_v2_kernel(
                     run(std::integral_constant<int, 3 * N / 4>{});
             } else if (cok) {
                 char *ob = static_cast<char *>(out) + ((size_t)c * stride + (size_t)blk * 8 * N) * out_bytes<CS16>();
+                ChMix cm;
+                if constexpr (NCO) cm = ch_mix_of(cn, c);   // cok: c < nch
                 auto put = [&](int idx, float2 o) {   // streaming (nt) stores, as the single-channel kernel's
+                    if constexpr (NCO) o = ch_mix(o, cm, blk * 8 * N + idx);
                     if constexpr (CS16) {
                         unsigned *p = reinterpret_cast<unsigned *>(ob) + idx;
                         if constexpr (SDDC_CH_NT) __builtin_nontemporal_store(cs16_pack(o, oa.scale), p);
@@ -391,12 +425,12 @@ constexpr int CHUNK_P = SDDC_CHUNK_P;
 #ifndef SDDC_CHP_HREG
 #define SDDC_CHP_HREG 1       // filter taps of the pass-0 bins in registers (else loaded per channel)
 #endif
-template <int D, bool RAND, bool CS16, bool L2X2>
+template <int D, bool RAND, bool CS16, bool L2X2, bool NCO = false>
 __global__ __launch_bounds__(NT, L2X2 ? SDDC_CHP_WAVES : 2) void r2iq_channels_p_kernel(
     const int *__restrict__ in32, void *__restrict__ out, size_t stride, int nframes,
     const int *__restrict__ tunebins, int nch, const float2 *__restrict__ tw_p1, const float2 *__restrict__ tw_q1,
     const float2 *__restrict__ rec_f, const float2 *__restrict__ rec_i, const float2 *__restrict__ post8192,
-    const float2 *__restrict__ hsel, OutArgs oa, float2 *__restrict__ scratch)
+    const float2 *__restrict__ hsel, OutArgs oa, float2 *__restrict__ scratch, ChNco cn)
 {
     constexpr int N = HALF >> D;
     static_assert(N >= 512, "d = 0..3");
@@ -572,15 +606,47 @@ __global__ __launch_bounds__(NT, L2X2 ? SDDC_CHP_WAVES : 2) void r2iq_channels_p
                 const __amdgpu_buffer_rsrc_t ro =
                     buf_rsrc(static_cast<char *>(out) + ((size_t)c * stride + (size_t)fbase) * out_bytes<CS16>());
                 const int r0 = k == 0 ? 4 : 0;
+                ChMix cm;
+                if constexpr (NCO) cm = ch_mix_of(cn, c);   // c < cend <= nch
 #pragma unroll
                 for (int r = 0; r < 12; r++) {
                     if (r < r0) continue;
-                    store_iq<CS16>(flip(u[r], oa.lsbmask), ro, (unsigned)jb, (unsigned)(NB * r), oa);
+                    float2 v = flip(u[r], oa.lsbmask);
+                    if constexpr (NCO) v = ch_mix(v, cm, fbase + jb + NB * r);
+                    store_iq<CS16>(v, ro, (unsigned)jb, (unsigned)(NB * r), oa);
                 }
             }
             __syncthreads();   // the slices are rewritten by the next group
         }
     }
+}
+
+// The lane-start chain of the per-channel NCO (FineTune::starts, fine_tune.cpp:47-57, in its float
+// operation order: plain mul/add, IEEE sqrt and divide, no contraction): thread (c, l) walks lane
+// l of channel c over the run's nb blocks of 128 samples and leaves the advanced state behind.
+constexpr int CHAIN_NT = 64;   // one wave per workgroup: 4 nch threads in all, spread over the CUs
+__global__ __launch_bounds__(CHAIN_NT) void channel_nco_chain_kernel(float2 *__restrict__ state,
+                                                                     const float2 *__restrict__ trig,
+                                                                     float2 *__restrict__ starts, int nch, int nb)
+{
+#pragma clang fp contract(off)
+    const int i = (int)(blockIdx.x * CHAIN_NT + threadIdx.x);   // 4 c + l
+    if (i >= 4 * nch) return;
+    const int c = i >> 2, l = i & 3;
+    const float2 t128 = trig[c * 32 + 31];   // the 128-step phasor T[31]
+    const float tr = t128.x, ti = t128.y;
+    const float2 s0 = state[i];
+    float cs = s0.x, sn = s0.y;
+    float2 *o = starts + (size_t)c * (size_t)nb * 4 + l;
+    for (int b = 0; b < nb; b++) {
+        o[(size_t)b * 4] = make_float2(cs, sn);
+        const float vc = tr * cs - ti * sn;
+        const float vs = ti * cs + tr * sn;
+        const float m = sqrtf(vc * vc + vs * vs);
+        cs = vc / m;
+        sn = vs / m;
+    }
+    state[i] = make_float2(cs, sn);
 }
 
 struct ChLaunch {
@@ -596,12 +662,16 @@ struct ChLaunch {
     int scratch_rows;
     int device;
     hipStream_t s;
+    const ChNco *nco;      // per-channel NCO tables of this launch, or nullptr (the plain instances)
 };
 
-template <int D, bool RAND, bool CS16, bool COMPACT, bool STAGE_OK>
+template <int D, bool RAND, bool CS16, bool COMPACT, bool STAGE_OK, bool NCO = false>
 hipError_t launch_v(const KernelTables &t, const ChLaunch &L)
 {
-    auto kern = r2iq_channels_v2_kernel<D, RAND, CS16, COMPACT, STAGE_OK>;
+    if constexpr (!NCO) {
+        if (L.nco) return launch_v<D, RAND, CS16, COMPACT, STAGE_OK, true>(t, L);
+    }
+    auto kern = r2iq_channels_v2_kernel<D, RAND, CS16, COMPACT, STAGE_OK, NCO>;
     int occ = 0, cus = 0;
     hipError_t e = launch_geometry(t.lc, reinterpret_cast<const void *>(kern), NT, L.device, &occ, &cus);
     if (e != hipSuccess) return e;
@@ -611,7 +681,7 @@ hipError_t launch_v(const KernelTables &t, const ChLaunch &L)
     float2 *scratch = grid <= L.scratch_rows ? L.scratch : nullptr;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NT), 0, L.s, reinterpret_cast<const int *>(L.d_in), L.d_out,
                        L.stride / 2, nframes, L.d_tunebins, L.nch, t.tw_p1, t.rec_f, t.post8192, t.hsel[D], L.oa,
-                       L.windows, scratch);
+                       L.windows, scratch, NCO ? *L.nco : ChNco{});
     return hipGetLastError();
 }
 
@@ -637,10 +707,13 @@ hipError_t launch_d(const KernelTables &t, const ChLaunch &L, int rand, int cs16
     return cs16 ? launch_c<D, false, true>(t, L) : launch_c<D, false, false>(t, L);
 }
 
-template <int D, bool RAND, bool CS16, bool L2X2>
+template <int D, bool RAND, bool CS16, bool L2X2, bool NCO = false>
 hipError_t launch_p2(const KernelTables &t, const ChLaunch &L)
 {
-    auto kern = r2iq_channels_p_kernel<D, RAND, CS16, L2X2>;
+    if constexpr (!NCO) {
+        if (L.nco) return launch_p2<D, RAND, CS16, L2X2, true>(t, L);
+    }
+    auto kern = r2iq_channels_p_kernel<D, RAND, CS16, L2X2, NCO>;
     int occ = 0, cus = 0;
     hipError_t e = launch_geometry(t.lc, reinterpret_cast<const void *>(kern), NT, L.device, &occ, &cus);
     if (e != hipSuccess) return e;
@@ -651,12 +724,12 @@ hipError_t launch_p2(const KernelTables &t, const ChLaunch &L)
         if (grid > L.scratch_rows) {   // one scratch row per workgroup: more workgroups than rows -> LDS form
             ChLaunch L0 = L;
             L0.scratch = nullptr;
-            return launch_p2<D, RAND, CS16, false>(t, L0);
+            return launch_p2<D, RAND, CS16, false, NCO>(t, L0);
         }
     }
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NT), 0, L.s, reinterpret_cast<const int *>(L.d_in), L.d_out,
                        L.stride / 2, nframes, L.d_tunebins, L.nch, t.tw_p1, t.tw_q1[D], t.rec_f, t.rec_i[D],
-                       t.post8192, t.hsel[D], L.oa, L.scratch);
+                       t.post8192, t.hsel[D], L.oa, L.scratch, NCO ? *L.nco : ChNco{});
     return hipGetLastError();
 }
 
@@ -693,10 +766,10 @@ hipError_t launch_pd(const KernelTables &t, const ChLaunch &L, int rand, int cs1
 
 hipError_t launch_channels_p(const KernelTables &t, int d, const int16_t *d_in, int nblk, const int *d_tunebins,
                              int nch, void *d_out, size_t stride, int lsb, int rand, int cs16, float cs16_scale,
-                             float2 *d_scratch, int scratch_rows, int device, hipStream_t s)
+                             float2 *d_scratch, int scratch_rows, int device, hipStream_t s, const ChNco *nco)
 {
     const ChLaunch L{d_in, nblk, d_tunebins, nch, d_out, stride, OutArgs{lsb ? 0x80000000u : 0u, cs16_scale},
-                     nullptr, d_scratch, scratch_rows, device, s};
+                     nullptr, d_scratch, scratch_rows, device, s, nco};
     switch (d) {
     case 0: return launch_pd<0>(t, L, rand, cs16);
     case 1: return launch_pd<1>(t, L, rand, cs16);
@@ -704,6 +777,15 @@ hipError_t launch_channels_p(const KernelTables &t, int d, const int16_t *d_in, 
     case 3: return launch_pd<3>(t, L, rand, cs16);
     default: return hipErrorInvalidValue;
     }
+}
+
+hipError_t launch_channel_nco_chain(float2 *d_state, const float2 *d_trig, float2 *d_starts, int nch, int nb,
+                                    hipStream_t s)
+{
+    if (nch <= 0 || nb <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(channel_nco_chain_kernel, dim3((unsigned)((4 * nch + CHAIN_NT - 1) / CHAIN_NT)), dim3(CHAIN_NT), 0,
+                       s, d_state, d_trig, d_starts, nch, nb);
+    return hipGetLastError();
 }
 
 bool channel_windows(int d, const int *tunebins, int nch, int2 *windows)
@@ -725,10 +807,10 @@ bool channel_windows(int d, const int *tunebins, int nch, int2 *windows)
 hipError_t launch_channels_v2(const KernelTables &t, int d, const int16_t *d_in, int nblk, const int *d_tunebins,
                               int nch, void *d_out, size_t stride, int lsb, int rand, int cs16, float cs16_scale,
                               const int2 *d_windows, float2 *d_scratch, int scratch_rows, int device,
-                              hipStream_t s)
+                              hipStream_t s, const ChNco *nco)
 {
     const ChLaunch L{d_in, nblk, d_tunebins, nch, d_out, stride, OutArgs{lsb ? 0x80000000u : 0u, cs16_scale},
-                     d_windows, d_scratch, scratch_rows, device, s};
+                     d_windows, d_scratch, scratch_rows, device, s, nco};
     switch (d) {
     case 4: return launch_d<4>(t, L, rand, cs16);
     case 5: return launch_d<5>(t, L, rand, cs16);

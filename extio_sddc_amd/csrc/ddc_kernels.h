@@ -121,21 +121,38 @@ hipError_t launch_frames_fs(const KernelTables &t, const int16_t *d_in, int nblk
                             const float2 *nco_starts, const float2 *nco_trig, unsigned *wq, const FsSched &fs,
                             int device, hipStream_t s);
 
+// Per-channel fine-tune NCO of the many-channel kernels (sddc_ddc_set_channel_fine_tune): device
+// tables of one run of a call.  Channel c mixes its output sample o of the run (o = 128 b + 4 q + l)
+// with T_c[q - 1] * S_c,b[l] (fine_tune.h), unless fc[c] == 0: that channel's output is the plain DDC.
+struct ChNco {
+    const float2 *starts = nullptr;   // [nch][nb][4] lane starts, written by launch_channel_nco_chain
+    const float2 *trig = nullptr;     // [nch][32] T of each channel's fc (host, FineTune::init)
+    const float *fc = nullptr;        // [nch]
+    int nb = 0;                       // 128-sample blocks per channel in the run
+};
+// The lane-start chain S_{b+1} = normalise(T[31] S_b) of every channel (FineTune::starts, bit for
+// bit), one thread per (channel, lane): reads state [nch][4], writes starts [nch][nb][4] and the
+// advanced state back, so the phase lives on the device.
+hipError_t launch_channel_nco_chain(float2 *d_state, const float2 *d_trig, float2 *d_starts, int nch, int nb,
+                                    hipStream_t s);
+
 // many-channel v2 (d = 4..6): persistent, forward once per (frame, 128-channel chunk)
 // stride: scalar components (float or int16) per channel row; cs16 as above.  d_windows:
 // per-128-channel-chunk forward-bin windows from channel_windows (device copy), or nullptr.
 // d_scratch: scratch_rows x 4096 float2, one row per workgroup, where a frame's split spectrum
 // is kept for its later chunks (used when the grid fits; nullptr = recompute per chunk).
+// nco: the per-channel NCO tables of this launch (the NCO instances of the kernel), or nullptr.
 hipError_t launch_channels_v2(const KernelTables &t, int d, const int16_t *d_in, int nblk, const int *d_tunebins,
                               int nch, void *d_out, size_t stride, int lsb, int rand, int cs16, float cs16_scale,
                               const int2 *d_windows, float2 *d_scratch, int scratch_rows, int device,
-                              hipStream_t s);
+                              hipStream_t s, const ChNco *nco = nullptr);
 // many-channel, d = 0..3: persistent, forward + split once per frame, 2^d channels' inverses
 // in flight.  d_scratch (scratch_rows x 4096 float2, >= CUs x 4 rows) holds each workgroup's
 // split spectrum in L2 instead of LDS; nullptr keeps it in LDS.
 hipError_t launch_channels_p(const KernelTables &t, int d, const int16_t *d_in, int nblk, const int *d_tunebins,
                              int nch, void *d_out, size_t stride, int lsb, int rand, int cs16, float cs16_scale,
-                             float2 *d_scratch, int scratch_rows, int device, hipStream_t s);
+                             float2 *d_scratch, int scratch_rows, int device, hipStream_t s,
+                             const ChNco *nco = nullptr);
 // host: the compact windows of every chunk; false if a chunk's window does not fit
 bool channel_windows(int d, const int *tunebins, int nch, int2 *windows);
 

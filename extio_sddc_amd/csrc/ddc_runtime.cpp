@@ -72,6 +72,14 @@ constexpr int kHistory = SDDC_DDC_HALF_FFT;
 constexpr int kBlock = SDDC_DDC_BLOCK;
 constexpr int kHostChunk = 32;   // blocks per pipeline chunk on the host path
 constexpr size_t kOutBlockMax = (size_t)SDDC_DDC_OUT_BLOCK * 2 * sizeof(float);   // bytes, CF32 d = 0
+// Per-channel NCO: the lane-start table holds 4 float2 per 128 output samples, i.e. 8192 >> d bytes
+// per channel and input block.  Its size is capped: a call whose table would be larger runs as
+// several runs of whole blocks.  128 MiB holds the bench's C5 step (1024 channels x 256 blocks at
+// d = 4) in one run; one block of 1024 channels at d = 0 needs 8 MiB, so a run is never empty.
+constexpr size_t kChNcoBlockBytes = (size_t)SDDC_DDC_OUT_BLOCK / sddc::FineTune::kBlock * sddc::FineTune::kLanes * sizeof(float2);
+constexpr size_t kChNcoTableCap = (size_t)128 << 20;
+static_assert(kChNcoBlockBytes == 8192, "4 lane starts per 128 output samples");
+static_assert(SDDC_DDC_MAX_CHANNELS * kChNcoBlockBytes <= kChNcoTableCap, "one block of every channel fits the cap");
 
 // The streams whose launches read a per-handle device table (the (P, Q) coefficients, the NCO
 // staging buffer, the channel tune bins, the channel scratch rows).  The C ABI accepts any
@@ -209,6 +217,18 @@ struct sddc_ddc {
     float2 *d_nco = nullptr;
     size_t d_nco_cap = 0;
 
+    // per-channel fine-tune NCO of the many-channel path (sddc_ddc_set_channel_fine_tune): T, fc and
+    // the lane-start state per channel on the device (the chain kernel advances the state, so a
+    // call needs no host round trip), and the lane-start table of one run of a call.  All are per
+    // handle: ch_readers orders the launches that touch them, a change of the fc array synchronises.
+    std::vector<float> chnco_fc;           // empty = off
+    float2 *d_chnco_trig = nullptr;        // [1024][32]
+    float2 *d_chnco_state = nullptr;       // [1024][4]
+    float *d_chnco_fc = nullptr;           // [1024]
+    float2 *d_chnco_starts = nullptr;      // [nch][run's 128-sample blocks][4]
+    size_t chnco_starts_cap = 0;           // bytes
+    int chnco_run_blocks = 0;              // SDDC_DDC_PARAM_CH_NCO_RUN_BLOCKS
+
     // history to start the next host-path call from (sddc_ddc_set_history)
     std::vector<int16_t> hist_override;
 
@@ -220,6 +240,15 @@ struct sddc_ddc {
     long inject_fail = -1;
     long inject_late = -1;   // SDDC_DDC_INJECT_FAIL_AFTER_D2H
 };
+
+// setFreqOffset's arithmetic (fft_mt_r2iq.cpp:104-106): the tune bin, clamped into [0, 4092],
+// and the residual tunebin/4096 - offset of the unclamped bin
+static int tuning_of(float offset, float *delta)
+{
+    const int tb = (int)(offset * SDDC_DDC_HALF_FFT / 4) * 4;
+    *delta = ((float)tb / SDDC_DDC_HALF_FFT) - offset;
+    return std::min(std::max(tb, 0), SDDC_DDC_HALF_FFT - 4);
+}
 
 static bool injected_failure(sddc_ddc_t *h)
 {
@@ -431,6 +460,10 @@ int sddc_ddc_destroy(sddc_ddc_t *h)
         if (h->d_tunebins) (void)hipFree(h->d_tunebins);
         if (h->d_windows) (void)hipFree(h->d_windows);
         if (h->d_chscratch) (void)hipFree(h->d_chscratch);
+        if (h->d_chnco_trig) (void)hipFree(h->d_chnco_trig);
+        if (h->d_chnco_state) (void)hipFree(h->d_chnco_state);
+        if (h->d_chnco_fc) (void)hipFree(h->d_chnco_fc);
+        if (h->d_chnco_starts) (void)hipFree(h->d_chnco_starts);
         if (h->d_pq) (void)hipFree(h->d_pq);
         if (h->d_fs) (void)hipFree(h->d_fs);
         if (h->d_queue) (void)hipFree(h->d_queue);
@@ -495,14 +528,23 @@ float sddc_ddc_set_freq_offset(sddc_ddc_t *h, float offset)
         fail(SDDC_ERR_ARG, "null handle");
         return 0.f;
     }
-    // fft_mt_r2iq.cpp:104-106
-    int tb = (int)(offset * SDDC_DDC_HALF_FFT / 4) * 4;
-    const float delta = ((float)tb / SDDC_DDC_HALF_FFT) - offset;
-    tb = std::min(std::max(tb, 0), SDDC_DDC_HALF_FFT - 4);
+    float delta;
+    const int tb = tuning_of(offset, &delta);
     std::lock_guard<std::mutex> lk(h->mu);
     const float ret = delta * (float)(1 << h->d);
     h->tunebin = tb;
     return ret;
+}
+
+int sddc_ddc_channel_tuning(float offset, int d, int *tunebin, float *relative_freq)
+{
+    if (!std::isfinite(offset)) return fail(SDDC_ERR_ARG, "channel_tuning: non-finite offset");
+    if (d < 0 || d >= SDDC_DDC_NDEC) return fail(SDDC_ERR_ARG, "channel_tuning: decimation index %d outside 0..6", d);
+    if (!tunebin || !relative_freq) return fail(SDDC_ERR_ARG, "channel_tuning: null result pointer");
+    float delta;
+    *tunebin = tuning_of(offset, &delta);
+    *relative_freq = delta * (float)(1 << d);
+    return SDDC_OK;
 }
 
 int sddc_ddc_reset(sddc_ddc_t *h)
@@ -707,6 +749,64 @@ int sddc_ddc_set_fine_tune(sddc_ddc_t *h, float relative_freq)
     return SDDC_OK;
 }
 
+int sddc_ddc_set_channel_fine_tune(sddc_ddc_t *h, const float *relative_freqs, int nch)
+{
+    using sddc::FineTune;
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    if (nch < 0 || nch > SDDC_DDC_MAX_CHANNELS)
+        return fail(SDDC_ERR_ARG, "channel fine tune: channel count %d outside 0..%d", nch, SDDC_DDC_MAX_CHANNELS);
+    if (!relative_freqs) nch = 0;
+    for (int c = 0; c < nch; c++)
+        if (!std::isfinite(relative_freqs[c]))
+            return fail(SDDC_ERR_ARG, "channel fine tune: non-finite frequency of channel %d", c);
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->cpu) return fail(SDDC_ERR_STATE, "channel fine tune: a CPU handle has no many-channel path");
+    if (nch == 0) {   // off; the next array, of any length, starts every channel at phase 0
+        h->chnco_fc.clear();
+        return SDDC_OK;
+    }
+    // RadioHandler.cpp:291-296 per channel index: re-init only on change; another nch restarts all
+    const bool all = h->chnco_fc.size() != (size_t)nch;
+    std::vector<char> changed((size_t)nch);
+    bool any = false;
+    for (int c = 0; c < nch; c++) any |= (changed[c] = all || relative_freqs[c] != h->chnco_fc[c]) != 0;
+    if (!any) return SDDC_OK;
+    DeviceGuard g(h->device);
+    HIP_TRY(g.err);
+    // earlier launches, on any stream, may still read the tables and advance the state
+    HIP_TRY(h->ch_readers.sync());
+    if (!h->d_chnco_trig) HIP_TRY(hipMalloc(&h->d_chnco_trig, SDDC_DDC_MAX_CHANNELS * FineTune::kTable * sizeof(float2)));
+    if (!h->d_chnco_state) HIP_TRY(hipMalloc(&h->d_chnco_state, SDDC_DDC_MAX_CHANNELS * FineTune::kLanes * sizeof(float2)));
+    if (!h->d_chnco_fc) HIP_TRY(hipMalloc(&h->d_chnco_fc, SDDC_DDC_MAX_CHANNELS * sizeof(float)));
+    h->chnco_fc.clear();   // a failed upload leaves the NCO off
+    std::vector<float2> trig((size_t)nch * FineTune::kTable), state((size_t)nch * FineTune::kLanes);
+    for (int c = 0; c < nch; c++) {
+        if (!changed[c]) continue;
+        FineTune ft;
+        ft.init(relative_freqs[c], 0.0f);
+        std::memcpy(&trig[(size_t)c * FineTune::kTable], ft.table(), FineTune::kTable * sizeof(float2));
+        ft.starts(1, &state[(size_t)c * FineTune::kLanes]);   // block 0's lane starts = the initial state
+    }
+    // synchronous copies of each run [c0, c1) of changed channels (unchanged ones keep their phase)
+    for (int c0 = 0; c0 < nch;) {
+        if (!changed[c0]) {
+            c0++;
+            continue;
+        }
+        int c1 = c0 + 1;
+        while (c1 < nch && changed[c1]) c1++;
+        const size_t n = (size_t)(c1 - c0);
+        HIP_TRY(hipMemcpy(h->d_chnco_trig + (size_t)c0 * FineTune::kTable, &trig[(size_t)c0 * FineTune::kTable],
+                          n * FineTune::kTable * sizeof(float2), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(h->d_chnco_state + (size_t)c0 * FineTune::kLanes, &state[(size_t)c0 * FineTune::kLanes],
+                          n * FineTune::kLanes * sizeof(float2), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(h->d_chnco_fc + c0, relative_freqs + c0, n * sizeof(float), hipMemcpyHostToDevice));
+        c0 = c1;
+    }
+    h->chnco_fc.assign(relative_freqs, relative_freqs + nch);
+    return SDDC_OK;
+}
+
 /* internal (sddc_ddc_internal.h): a tuning parameter of the kernels, for A/B timing */
 int sddc_ddc_internal_set_param(sddc_ddc_t *h, int param, int value)
 {
@@ -746,6 +846,11 @@ int sddc_ddc_internal_set_param(sddc_ddc_t *h, int param, int value)
     case SDDC_DDC_PARAM_FS_STEAL_PUBLIC:
         if (value < 0 || value > 1024) return fail(SDDC_ERR_ARG, "public frames %d outside 0..1024", value);
         h->fs_sched.pub = value;
+        return SDDC_OK;
+    case SDDC_DDC_PARAM_CH_NCO_RUN_BLOCKS:
+        if (value < 0 || value > SDDC_DDC_MAX_BLOCKS)
+            return fail(SDDC_ERR_ARG, "run blocks %d outside 0..%d", value, SDDC_DDC_MAX_BLOCKS);
+        h->chnco_run_blocks = value;
         return SDDC_OK;
     default:
         return fail(SDDC_ERR_ARG, "unknown parameter %d", param);
@@ -791,7 +896,13 @@ int sddc_ddc_process_channels_device(sddc_ddc_t *h, const int16_t *d_in, int nbl
     for (int c = 0; c < nch; c++)
         if (tunebins[c] < 0 || tunebins[c] >= SDDC_DDC_HALF_FFT)
             return fail(SDDC_ERR_ARG, "channel %d tune bin %d outside [0,4096)", c, tunebins[c]);
-    if (h->nco_fc != 0.f) return fail(SDDC_ERR_STATE, "fine-tune NCO is single-channel; set it to 0 first");
+    if (h->nco_fc != 0.f)
+        return fail(SDDC_ERR_STATE, "set_fine_tune's NCO is single-channel; set it to 0 first "
+                                    "(channels: sddc_ddc_set_channel_fine_tune)");
+    const bool nco = !h->chnco_fc.empty();
+    if (nco && h->chnco_fc.size() != (size_t)nch)
+        return fail(SDDC_ERR_STATE, "per-channel fine tune is set for %zu channels, the call has %d",
+                    h->chnco_fc.size(), nch);
     const size_t need = (size_t)nblk * (size_t)(SDDC_DDC_OUT_BLOCK >> h->d) * 2;
     if (nch > 1 && out_stride < need)
         return fail(SDDC_ERR_ARG, "out_stride %zu < %zu components per channel", out_stride, need);
@@ -838,16 +949,50 @@ int sddc_ddc_process_channels_device(sddc_ddc_t *h, const int16_t *d_in, int nbl
         h->chscratch_rows = cus * 4;
     }
     // the scratch rows are per handle: a launch must not overlap one on another stream
-    if (h->d_chscratch) HIP_TRY(h->ch_readers.order_before(s));
-    if (v2)
-        HIP_TRY(sddc::launch_channels_v2(h->tables, h->d, d_in, nblk, h->d_tunebins, nch, d_out, out_stride,
-                                         h->lsb, h->rand, cs16, h->cs16_scale, windows, h->d_chscratch,
-                                         h->chscratch_rows, h->device, s));
-    else
-        HIP_TRY(sddc::launch_channels_p(h->tables, h->d, d_in, nblk, h->d_tunebins, nch, d_out, out_stride,
-                                        h->lsb, h->rand, cs16, h->cs16_scale, h->d_chscratch, h->chscratch_rows,
-                                        h->device, s));
-    HIP_TRY(h->ch_readers.record(s));
+    // (so are the per-channel NCO's state and tables)
+    if (h->d_chscratch || nco) HIP_TRY(h->ch_readers.order_before(s));
+    auto launch = [&](const int16_t *in, int n, void *out, const sddc::ChNco *cn) {
+        if (v2)
+            return sddc::launch_channels_v2(h->tables, h->d, in, n, h->d_tunebins, nch, out, out_stride, h->lsb,
+                                            h->rand, cs16, h->cs16_scale, windows, h->d_chscratch,
+                                            h->chscratch_rows, h->device, s, cn);
+        return sddc::launch_channels_p(h->tables, h->d, in, n, h->d_tunebins, nch, out, out_stride, h->lsb, h->rand,
+                                       cs16, h->cs16_scale, h->d_chscratch, h->chscratch_rows, h->device, s, cn);
+    };
+    if (!nco) {
+        HIP_TRY(launch(d_in, nblk, d_out, nullptr));
+        HIP_TRY(h->ch_readers.record(s));
+        return SDDC_OK;
+    }
+    // Per-channel NCO: runs of whole blocks, each a chain launch (the run's lane starts, the state
+    // advanced on the device) and a channels launch over the run's blocks with their 4096-sample
+    // halo.  The channels kernels are stateless per (frame, chunk), so the cut changes no bit.
+    const size_t blk_bytes = (size_t)nch * (size_t)(kChNcoBlockBytes >> h->d);   // table bytes per input block
+    int run = (int)std::min<size_t>((size_t)nblk, std::max<size_t>(1, kChNcoTableCap / blk_bytes));
+    if (h->chnco_run_blocks > 0) run = std::min(run, h->chnco_run_blocks);
+    if ((size_t)run * blk_bytes > h->chnco_starts_cap) {   // earlier launches may still read the old table
+        HIP_TRY(h->ch_readers.sync());
+        HIP_TRY(hipStreamSynchronize(s));
+        if (h->d_chnco_starts) (void)hipFree(h->d_chnco_starts);
+        h->d_chnco_starts = nullptr;
+        h->chnco_starts_cap = 0;
+        HIP_TRY(hipMalloc(&h->d_chnco_starts, (size_t)run * blk_bytes));
+        h->chnco_starts_cap = (size_t)run * blk_bytes;
+    }
+    const int per_blk = SDDC_DDC_OUT_BLOCK >> h->d;                      // complex samples per block
+    const int nb_blk = per_blk / sddc::FineTune::kBlock;                 // 128-sample blocks per block
+    const size_t out_blk = (size_t)per_blk * (cs16 ? 4 : 8);             // bytes per channel and block
+    for (int b0 = 0; b0 < nblk; b0 += run) {
+        const int n = std::min(run, nblk - b0);
+        const sddc::ChNco cn{h->d_chnco_starts, h->d_chnco_trig, h->d_chnco_fc, n * nb_blk};
+        hipError_t e = sddc::launch_channel_nco_chain(h->d_chnco_state, h->d_chnco_trig, h->d_chnco_starts, nch,
+                                                      cn.nb, s);
+        if (e == hipSuccess) e = launch(d_in + (size_t)b0 * kBlock, n, static_cast<char *>(d_out) + (size_t)b0 * out_blk, &cn);
+        // the launches so far stay ordered against other streams and the next fc change
+        const hipError_t er = h->ch_readers.record(s);
+        HIP_TRY(e);
+        HIP_TRY(er);
+    }
     return SDDC_OK;
 }
 

@@ -34,6 +34,11 @@ extern "C" {
  * bytes w0 | w1 << 8 | w2 << 16 | w3 << 24 (CU slot 0 in the low byte, each 1..127); 0: the
  * built-in kFsSlotWeights (A/B of the weights). */
 #define SDDC_DDC_PARAM_FS_SLOT_WEIGHTS 8
+/* SDDC_DDC_PARAM_CH_NCO_RUN_BLOCKS = n > 0: with the per-channel NCO on, process_channels_device
+ * cuts a call into runs of at most n input blocks (a chain launch + a channels launch each); 0
+ * (default): as many blocks as the lane-start table's byte cap holds (ddc_runtime.cpp
+ * kChNcoTableCap), which bounds n > 0 too.  The cut changes no output bit (tests). */
+#define SDDC_DDC_PARAM_CH_NCO_RUN_BLOCKS 9
 
 int sddc_ddc_internal_set_param(sddc_ddc_t *h, int param, int value);
 /* Diagnostic stamp buffers of -DSDDC_STAMPS builds (tools/fs_stamps.py); -1 in product builds. */

@@ -62,6 +62,20 @@ def filter_response(gain: float, d: int) -> np.ndarray:
     return out[:, 0] + 1j * out[:, 1]
 
 
+def channel_tuning(offsets, d: int):
+    """setFreqOffset's arithmetic per channel, without a handle (sddc_ddc_channel_tuning):
+    offsets (fractions of Fs/2) -> (tunebins int32, fcs float32) for process_channels_device and
+    R2iq.setChannelFineTune."""
+    L = _lib.load()
+    off = np.asarray(offsets, np.float32).reshape(-1)
+    tbs, fcs = np.empty(off.size, np.int32), np.empty(off.size, np.float32)
+    tb, fc = ctypes.c_int(0), ctypes.c_float(0.0)
+    for i, o in enumerate(off):
+        check(L.sddc_ddc_channel_tuning(float(o), d, ctypes.byref(tb), ctypes.byref(fc)))
+        tbs[i], fcs[i] = tb.value, fc.value
+    return tbs, fcs
+
+
 def device_count() -> int:
     return _lib.load().sddc_ddc_device_count()
 
@@ -141,6 +155,17 @@ class R2iq:
         750-856 via RadioHandler.cpp:33-37); fc = the residual from setFreqOffset, 0 = off.
         A new fc restarts the phase at 0, the same fc keeps it (RadioHandler.cpp:291-296)."""
         check(self._L.sddc_ddc_set_fine_tune(self._h, float(fc)))
+
+    def setChannelFineTune(self, fcs) -> None:
+        """Per-channel fine-tune NCO of process_channels_device: fcs[c] is channel c's fc (see
+        channel_tuning), 0 leaves that channel unmixed; None or empty turns it off.  Per channel
+        index an unchanged fc keeps the phase, a changed one restarts it at 0; another channel
+        count restarts all (sddc_ddc_set_channel_fine_tune)."""
+        if fcs is None or len(fcs) == 0:
+            check(self._L.sddc_ddc_set_channel_fine_tune(self._h, None, 0))
+            return
+        fc = np.ascontiguousarray(np.asarray(fcs, np.float32).reshape(-1))
+        check(self._L.sddc_ddc_set_channel_fine_tune(self._h, fc.ctypes.data, fc.size))
 
     def setTuneBin(self, tunebin: int) -> None:
         check(self._L.sddc_ddc_set_tunebin(self._h, tunebin))

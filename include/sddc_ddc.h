@@ -42,7 +42,9 @@ extern "C" {
 #endif
 
 #define SDDC_DDC_ABI_VERSION 3   /* 2: + set_fine_tune, set_output_format, process_blocks, register_host;
-                                    3: + CPU handles (SDDC_DDC_DEVICE_CPU), backend, set_history */
+                                    3: + CPU handles (SDDC_DDC_DEVICE_CPU), backend, set_history;
+                                       still 3: + set_channel_fine_tune, channel_tuning (new symbols
+                                       only, no existing call changed) */
 
 #define SDDC_DDC_HALF_FFT   4096    /* halfFft               fft_mt_r2iq.h:18 */
 #define SDDC_DDC_FFTN       8192    /* FFTN_R_ADC            config.h:49 */
@@ -121,10 +123,35 @@ int   sddc_ddc_set_history(sddc_ddc_t *h, const int16_t *last4096);
  * sddc_ddc_set_freq_offset; a new fc restarts the phase at 0 like
  * shift_limited_unroll_C_sse_init(fc, 0) (RadioHandler.cpp:291-296), the same fc keeps
  * it; 0 turns the mixer off.  While on, process_device / process_host advance the
- * mixer phase by their output length (stream order), and the single-channel path
- * only: process_channels_device returns SDDC_ERR_STATE.  Not for the drop-in class,
- * whose caller (RadioHandler) still mixes on the CPU. */
+ * mixer phase by their output length (stream order).  This one fc belongs to the
+ * single-channel path: while it is non-zero process_channels_device returns
+ * SDDC_ERR_STATE; the many-channel path has an NCO per channel,
+ * sddc_ddc_set_channel_fine_tune below.  Not for the drop-in class, whose caller
+ * (RadioHandler) still mixes on the CPU. */
 int   sddc_ddc_set_fine_tune(sddc_ddc_t *h, float relative_freq);
+
+/* The same mixer per channel of the many-channel path: relative_freqs[c] is channel c's fc
+ * (host array of nch floats, 0 <= nch <= SDDC_DDC_MAX_CHANNELS; the meaning of
+ * sddc_ddc_set_fine_tune's relative_freq).  NULL or nch == 0 turns it off.  A channel whose fc
+ * is 0 is not mixed: its output is the plain DDC bit for bit.  Re-init rule per channel index
+ * (RadioHandler.cpp:291-296), in stream order: an fc equal to the one already set keeps that
+ * channel's phase, a changed fc restarts that channel at phase 0, another nch restarts every
+ * channel.  While on, every process_channels_device call advances each channel's phase by its
+ * output length; the phases live on the device (the lane-start chain of fine_tune.h runs there),
+ * so a call makes no host round trip.  sddc_ddc_reset keeps the phases.  A change of the array
+ * waits for the handle's many-channel launches in flight.  process_channels_device with another
+ * channel count than nch returns SDDC_ERR_STATE; process_device and the host calls ignore the
+ * setting.  Errors: a non-finite fc or nch outside 0..1024 SDDC_ERR_ARG, a CPU handle
+ * SDDC_ERR_STATE.
+ * Memory: the lane starts of a call take nch * nblk * (8192 >> d) bytes of device memory, at
+ * most 128 MiB per handle; a larger call runs as several launches over whole blocks, with
+ * identical output. */
+int   sddc_ddc_set_channel_fine_tune(sddc_ddc_t *h, const float *relative_freqs, int nch);
+/* setFreqOffset's arithmetic (fft_mt_r2iq.cpp:101-109) without a handle, to fill the tune bin
+ * and fc arrays of the many-channel calls: *tunebin = int(offset*1024)*4 clamped into [0, 4092],
+ * *relative_freq = (tunebin/4096 - offset) * 2^d of the unclamped bin, the same float operations
+ * as sddc_ddc_set_freq_offset.  SDDC_ERR_ARG for a non-finite offset, d outside 0..6 or NULL. */
+int   sddc_ddc_channel_tuning(float offset, int d, int *tunebin, float *relative_freq);
 
 /* Complex samples produced per nblk input blocks at decimation d: nblk*(32768>>d). */
 size_t sddc_ddc_output_samples(int d, int nblk);
@@ -154,7 +181,8 @@ int sddc_ddc_process_device(sddc_ddc_t *h, const int16_t *d_in, int nblk,
  * frame, shared by `nch` channels with their own tune bins (host array, each a
  * multiple of 4 in [0,4096)).  Channel c's stream starts `c*out_stride`
  * components (floats for CF32, int16 for CS16; 2 per complex sample) into
- * d_out.  All channels use the handle's d/sideband/rand/output format. */
+ * d_out.  All channels use the handle's d/sideband/rand/output format, and each its own
+ * fine-tune NCO when sddc_ddc_set_channel_fine_tune is on (nch must match). */
 int sddc_ddc_process_channels_device(sddc_ddc_t *h, const int16_t *d_in, int nblk,
                                      const int *tunebins, int nch,
                                      void *d_out, size_t out_stride,

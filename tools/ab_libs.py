@@ -28,6 +28,10 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--tunebin", type=int, default=1024)
     ap.add_argument("--channels", type=int, default=0, help="time process_channels_device with tune bins 4c")
+    ap.add_argument("--channel-nco", action="store_true",
+                    help="with --channels: the per-channel fine-tune NCO on, channel c at its residual for an offset "
+                         "between its tune bins (distinct non-zero fcs), on every library; for one library only "
+                         "append :nco=1 to it (LIB.so:nco=1 next to LIB.so times NCO on against off)")
     ap.add_argument("--rand", action="store_true", help="RAND de-randomisation on (config C4)")
     ap.add_argument("--lsb", action="store_true", help="sideband inversion on (config C4)")
     ap.add_argument("--input", choices=["rand", "bench", "zeros"], default="rand",
@@ -38,14 +42,23 @@ def main():
     import torch
     from extio_sddc_amd._lib import SIGNATURES
     dev = torch.device("cuda", 0)
-    libs, handles = [], []
+    libs, handles, nco_on = [], [], []
     for spec in args.libs:
-        # LIB.so or LIB.so:PARAM=VALUE[,PARAM=VALUE] (sddc_ddc_internal_set_param on its handle)
+        # LIB.so or LIB.so:PARAM=VALUE[,PARAM=VALUE] (sddc_ddc_internal_set_param on its handle;
+        # nco=1: the per-channel NCO on for this library)
         p, _, params = spec.partition(":")
         L = ctypes.CDLL(os.path.abspath(p))
         for name, (res, a) in SIGNATURES.items():
-            fn = getattr(L, name)
+            fn = getattr(L, name, None)
+            if fn is None:   # a library of an older revision lacks the newer symbols
+                continue
             fn.restype, fn.argtypes = res, a
+        nco = args.channel_nco
+        if "nco=1" in params.split(","):
+            nco, params = True, ",".join(kv for kv in params.split(",") if kv != "nco=1")
+        assert not nco or (args.channels and hasattr(L, "sddc_ddc_set_channel_fine_tune")), \
+            f"{p}: the per-channel NCO needs --channels and a library that has it"
+        nco_on.append(nco)
         h = ctypes.c_void_p()
         rc = L.sddc_ddc_create(1.0, 0, ctypes.byref(h))
         assert rc == 0, L.sddc_ddc_last_error()
@@ -85,8 +98,18 @@ def main():
         outs = [torch.empty(n_out * nch, dtype=torch.float32, device=dev) for _ in libs]
         tbs = np.ascontiguousarray(np.arange(nch, dtype=np.int32) * 4)
         times = [[] for _ in libs]
-        for L, h in zip(libs, handles):
+        for L, h, nco in zip(libs, handles, nco_on):
             L.sddc_ddc_set_decimation(h, d)
+            if nco:
+                # channel c tuned 0.5 .. 3.5 bins above its tune bin 4c: its residual is its fc
+                fcs = np.empty(nch, np.float32)
+                tb, fc = ctypes.c_int(0), ctypes.c_float(0.0)
+                for c in range(nch):
+                    off = (4 * c + 0.5 + 3.0 * c / nch) / 4096
+                    assert L.sddc_ddc_channel_tuning(off, d, ctypes.byref(tb), ctypes.byref(fc)) == 0
+                    assert tb.value == tbs[c] and fc.value != 0.0
+                    fcs[c] = fc.value
+                assert L.sddc_ddc_set_channel_fine_tune(h, fcs.ctypes.data, nch) == 0, L.sddc_ddc_last_error()
         # every variant's output is checked on its own first call into a NaN-filled buffer: a
         # variant that leaves frames unwritten shows NaN (later calls reuse the buffer, so a
         # comparison after the timed rounds alone would not see it)
@@ -122,9 +145,10 @@ def main():
             diff = ((outs[i] - outs[0]).abs().max() / outs[0].abs().max()).item()
             gs = nblk * 65536 / (med * 1e-3) / 1e9
             frac = nblk * 65536 * (2 + 4 * nch / (1 << d)) / (med * 1e-3) / 8e12
-            res[f"d{d}:{os.path.basename(p)}#{i}"] = {"median_ms": med, "min_ms": ts[0], "GSps": gs, "hbm_frac": frac,
+            res[f"d{d}:{os.path.basename(p)}#{i}"] = {"median_ms": med, "min_ms": ts[0], "max_ms": ts[-1], "GSps": gs,
+                                                  "hbm_frac": frac, "channel_nco": nco_on[i],
                                                   "maxrel_vs_first": diff, "unwritten_floats": unwritten[i]}
-            print(f"d={d} {os.path.basename(p):28s} median {med:.3f} ms min {ts[0]:.3f}  {gs:7.1f} GS/s  "
+            print(f"d={d} {os.path.basename(p):28s} median {med:.3f} ms min {ts[0]:.3f} max {ts[-1]:.3f}  {gs:7.1f} GS/s  "
                   f"roofline {frac*100:5.1f}%  maxrel vs first {diff:.2e}"
                   + (f"  INCOMPLETE: {unwritten[i]} floats unwritten" if unwritten[i] else ""), flush=True)
     print(json.dumps(res))
