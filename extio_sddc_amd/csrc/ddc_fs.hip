@@ -32,8 +32,9 @@
 //
 // Layout for MI355X: one 256-thread workgroup (4 wave64) per frame in flight, 4 workgroups per
 // CU (40 852 B of LDS each fill the 160 KB), persistent grid (CUs x 4) fed by the slot-weighted
-// static frame split of ddc_queue.hpp (queue, work stealing: options), the next frame's input prefetched into
-// registers under inverse pass 1, all global memory through raw buffer instructions (scalar base
+// static frame split of ddc_queue.hpp (at full residency with per-workgroup shares learnt from the
+// workgroups' measured end times, fs_split_controller.hpp; queue, work stealing: options), the
+// next frame's input prefetched into registers under inverse pass 1, all global memory through raw buffer instructions (scalar base
 // + lane offset), nt IQ stores.
 #include <hip/hip_runtime.h>
 
@@ -178,7 +179,8 @@ template <int SCHED, int ZR, bool RAND, bool LSB, bool NCO, bool CS16>
 __global__ __launch_bounds__(NT, 4) void r2iq_fs_kernel(
     const int *__restrict__ in32, void *__restrict__ out, int nframes, const float2 *__restrict__ tw_p1,
     const float2 *__restrict__ rec_f, const float4 *__restrict__ pqf, const float2 *__restrict__ fsl, int tunebin,
-    OutArgs oa, NcoArgs nco, unsigned *__restrict__ wq, int ns, unsigned slotw, int xmap, int minrem, int pub)
+    OutArgs oa, NcoArgs nco, unsigned *__restrict__ wq, int ns, unsigned slotw, int xmap, int minrem, int pub,
+    unsigned *__restrict__ tlog, unsigned ttag, int use_tab, FsShares shares)
 {
     __shared__ __attribute__((aligned(16))) float2 lds[kFsLds];
     // F1 twiddles W_256^{s r} [15][16] (I1 conjugates them: at d = 0 its table is the same) and
@@ -198,16 +200,28 @@ __global__ __launch_bounds__(NT, 4) void r2iq_fs_kernel(
     constexpr int QLANE = 64 * kQWave;
     const bool qw = __builtin_amdgcn_readfirstlane(tid >> 6) == kQWave;
     typename SchedOf<SCHED>::T fsch;
+    // the static schedule's split: the launch's share table or the slot weights (ddc_queue.hpp);
+    // the queue and stealing schedules keep the slot weights
+    auto split = [&](int G, int v) __attribute__((always_inline)) {
+        if constexpr (SCHED == kSchedStatic) return fs_static_split(ns, G, v, slotw, use_tab, shares);
+        else return slot_split(ns, G, v, slotw);
+    };
+    // the adaptive split's measurement (static schedule, tlog != 0): the workgroup's start, with
+    // its end written once at exit (below); nothing of it inside the frame loop
+    unsigned t_start = 0u;
+    if constexpr (SCHED == kSchedStatic)
+        if (tlog) t_start = (unsigned)__builtin_amdgcn_s_memrealtime();
     int x[16];
     {
         // every wave knows the first frame (it is static unless the batch is small): its input
         // loads go out at once, ahead of the table copies
-        const int G = (int)gridDim.x, a0 = slot_split(ns, G, w, slotw);
-        const int f0s = a0 < slot_split(ns, G, w + 1, slotw) ? a0 : -1;
+        const int G = (int)gridDim.x, a0 = split(G, w), b0 = split(G, w + 1);
+        const int f0s = a0 < b0 ? a0 : -1;
         if (f0s >= 0) load_frame(in32, f0s / FRAMES, f0s % FRAMES, x);
         if (qw) {
             int f0[1];
             if constexpr (SCHED == kSchedSteal) fsch.init(wq, nframes, ns, w, G, slotw, f0, minrem, pub);
+            else if constexpr (SCHED == kSchedStatic) fsch.init_range(a0, b0, f0);
             else fsch.init(wq, nframes, ns, w, G, slotw, f0);
             if (tid == QLANE) s_next = f0[0];
         }
@@ -268,7 +282,7 @@ __global__ __launch_bounds__(NT, 4) void r2iq_fs_kernel(
     }
     int pA = -1, fend = -1;
     {
-        const int G = (int)gridDim.x, a = slot_split(ns, G, w, slotw), b = slot_split(ns, G, w + 1, slotw);
+        const int G = (int)gridDim.x, a = split(G, w), b = split(G, w + 1);
         if constexpr (SCHED == kSchedStatic) {
             pA = b + 2;
             fend = b;
@@ -556,6 +570,14 @@ __global__ __launch_bounds__(NT, 4) void r2iq_fs_kernel(
         while (f >= 0) frame(std::true_type{});
     }
     ST_WRITE(g_fs_stamps, w, tid);
+    if constexpr (SCHED == kSchedStatic) {
+        // one lane, one 16-byte vector store to the launch's slot of the handle's host-mapped ring:
+        // {start, end, tag, check}; the host takes an entry only with its launch's tag and check
+        if (tlog && tid == 0) {
+            const unsigned t_end = (unsigned)__builtin_amdgcn_s_memrealtime();
+            reinterpret_cast<uint4 *>(tlog)[w] = make_uint4(t_start, t_end, ttag, t_start ^ t_end ^ ttag);
+        }
+    }
     if constexpr (SCHED == kSchedQueue)
         if (tid == QLANE) fs_queue_done(wq, (unsigned)gridDim.x);
 }
@@ -623,6 +645,16 @@ hipError_t launch_fs_s(const KernelTables &t, const int16_t *d_in, int nblk, voi
     if (grid > nframes) grid = nframes;
     int ns = frame_schedule_static(nframes, static_pct);
     unsigned slotw = occ == 4 && grid == cus * occ ? (fs.slotw ? fs.slotw : kFsSlotWeights) : 0u;
+    // the adaptive split: a full-residency launch of the static schedule with the built-in weights
+    // takes its share table and its measurement slot from the handle's controller
+    const FsShares *tab = nullptr;
+    unsigned *tlog = nullptr, ttag = 0u;
+    if (SCHED == kSchedStatic && fs.adapt && slotw != 0u && fs.slotw == 0u && fpw <= 0 && grid <= kFsShareMaxG &&
+        !fs.adapt(fs.adapt_ctx, grid, ns, &tab, &tlog, &ttag)) {
+        tab = nullptr;
+        tlog = nullptr;
+    }
+    static const FsShares kNoShares = {};
     int xmap = 0;
     if (fpw > 0) {   // non-persistent: fpw frames per workgroup, the hardware dispatcher balances
         grid = (nframes + fpw - 1) / fpw;
@@ -636,7 +668,8 @@ hipError_t launch_fs_s(const KernelTables &t, const int16_t *d_in, int nblk, voi
     // past either runs the static split alone (minrem 0)
     if (SCHED == kSchedSteal && (grid > kFsStealMax || 2LL * nframes / grid + 1 > kStealMaxRange)) minrem = 0;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NT), 0, s, reinterpret_cast<const int *>(d_in), d_out, nframes,
-                       t.tw_p1, t.rec_f, pqf, fsl, tunebin, oa, nco, wq, ns, slotw, xmap, minrem, fs.pub);
+                       t.tw_p1, t.rec_f, pqf, fsl, tunebin, oa, nco, wq, ns, slotw, xmap, minrem, fs.pub, tlog, ttag,
+                       tab ? 1 : 0, tab ? *tab : kNoShares);
     return hipGetLastError();
 }
 

@@ -8,6 +8,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "fs_shares.h"
+
 namespace sddc {
 
 // Launch geometry, per handle: the device's CU count and, per kernel (function pointer), the
@@ -115,6 +117,14 @@ struct FsSched {
     int pub = 0;   // frames at the end of each range open to thieves (0: all but the first two)
     int zr = 1;    // skip the tune bin's whole zero rows of the inverse input (0: never; A/B)
     unsigned slotw = 0u;   // the static split's slot weights (slot_weights4 packing); 0: kFsSlotWeights
+    // The adaptive split's hook (fs_split_controller.hpp; ddc_runtime.cpp fs_adapt_prepare), or
+    // null: called for a launch of the static schedule at full residency (G = 4 x CUs <=
+    // kFsShareMaxG workgroups, ns frames) with the built-in weights.  *tab: the launch's share table
+    // (fs_shares.h), null for the built-in split; *tlog: G x 4 words of host-mapped memory where
+    // each workgroup writes {start, end, tag, start ^ end ^ tag} as it exits (the constant-rate
+    // 100 MHz counter's low words), or null.  false: the launch runs as without the hook.
+    bool (*adapt)(void *ctx, int G, int ns, const FsShares **tab, unsigned **tlog, unsigned *tag) = nullptr;
+    void *adapt_ctx = nullptr;
 };
 hipError_t launch_frames_fs(const KernelTables &t, const int16_t *d_in, int nblk, void *d_out, const float4 *pqf,
                             const float2 *fsl, int tunebin, int lsb, int rand, int cs16, float cs16_scale,

@@ -9,7 +9,7 @@
 namespace sddc {
 namespace {
 
-// Why not a plain static split.  A full-residency launch (grid = 4 x CUs) places blockIdx quarter
+// Why not a plain equal split.  A full-residency launch (grid = 4 x CUs) places blockIdx quarter
 // q on CU slot q (HW_ID TG_ID, all 1024 workgroups; profiles/r04/stamps/*by_slot*), and a CU's
 // SIMDs arbitrate by age, so slot q runs at a fixed fraction of slot 0's speed (d = 4: 1, 0.89,
 // 0.74, 0.59 frames per us while all four are resident).  An equal contiguous split left slot 0
@@ -22,6 +22,15 @@ namespace {
 // not predict and ends the launch frame-granular (the FS kernel, d = 0).  The persistent kernel
 // (d >= 1) uses the weighted split alone: there the queue's per-frame cost was larger than the
 // imbalance it removed (ddc_persistent.hip).
+//
+// The FS kernel's default since then is the static split alone (StaticSchedule below: the queue
+// and work stealing both put per-frame work into the frame loop and measured slower), and at full
+// residency its ranges come from a per-workgroup cumulative-share table in the kernel arguments
+// (fs_static_split, fs_shares.h) that the host learns from the workgroups' measured end times
+// (fs_split_controller.hpp): blockIdx lands on the same CU and slot in every launch, and 7.4 of
+// the 7.8 us rms spread of the end times repeated from launch to launch
+// (profiles/adaptive_split/before_repeat.txt).  slot_split stays for every other launch: below
+// full residency, explicit slot weights, the cold start, the queue and stealing schedules, d >= 1.
 //
 // The queue: 8 shards of consecutive frames (one counter each, on its own 64-B line); a workgroup
 // starts on shard blockIdx % 8 (its XCD under round-robin placement: neighbouring frames, which
@@ -51,6 +60,14 @@ __device__ __forceinline__ int slot_split(int ns, int G, int v, unsigned slotw)
         else if (k == q) sw += (long long)i * wk;
     }
     return (int)(((long long)ns * sw) / tot);
+}
+
+// first frame of workgroup v of the static schedule's split: from the launch's cumulative-share
+// table in the kernel arguments (fs_shares.h: the adaptive split, tab != 0) or the slot weights.
+// The table is read by scalar loads from the kernel argument segment, once, before the frame loop.
+__device__ __forceinline__ int fs_static_split(int ns, int G, int v, unsigned slotw, int tab, const FsShares &sh)
+{
+    return tab ? fs_share_start(ns, G, v, sh) : slot_split(ns, G, v, slotw);
 }
 
 // The queue is worked by one wave (wave-uniform, so the bookkeeping is scalar); only the atomic
@@ -180,8 +197,15 @@ struct FrameSchedule {
 
 // The static schedule: the slot-weighted split alone (no atomics).  Same interface as
 // FrameSchedule<1> and StealSchedule (init / peek / next / take), worked by the queue wave.
+// init_range: the range [a, b) given (fs_static_split: the share table's or the slot weights').
 struct StaticSchedule {
     int nxt, end;
+    __device__ __forceinline__ void init_range(int a, int b, int (&f)[1])
+    {
+        f[0] = a < b ? a : -1;
+        nxt = a + 1;
+        end = b;
+    }
     __device__ __forceinline__ void init(unsigned *, int, int ns, int w, int G, unsigned slotw, int (&f)[1])
     {
         const int a = slot_split(ns, G, w, slotw), b = slot_split(ns, G, w + 1, slotw);

@@ -24,6 +24,7 @@
 #include "ddc_kernels.h"
 #include "filterbank.h"
 #include "fine_tune.h"
+#include "fs_split_controller.hpp"
 #include "sddc_fft.h"
 #include "sddc_ddc.h"
 #include "sddc_ddc_internal.h"
@@ -201,6 +202,43 @@ struct sddc_ddc {
     int slot_weights = sddc::kSlotWeighting;    // the persistent kernel's slot-weighted split (ddc_queue.hpp)
     sddc::FsSched fs_sched;                    // the d = 0 kernel's frame schedule (ddc_kernels.h)
     hipStream_t q_s[kQueueSlots] = {};
+
+    // The d = 0 kernel's adaptive static split (fs_split_controller.hpp), all under mu.  Each
+    // full-residency launch of the static schedule takes a slot of a ring in host-mapped pinned
+    // memory, where its workgroups write {start, end, tag, check} as they exit, and the share table
+    // the controller built from the launches measured so far (in the kernel arguments: no device
+    // table, no stream operation).  The next such launch picks up whatever slots are complete: an
+    // entry counts only with its launch's tag and check word, so a slot that is stale, partly
+    // written or overwritten by a launch that ran late is simply not complete (and is dropped when
+    // its turn in the ring comes again).  A launch on another stream than the one before it may
+    // overlap it: it, the one before it and the next kTaint launches are not used.
+    struct FsAdapt {
+        static constexpr int kRing = 16;
+        static constexpr int kTaint = 4;
+        static constexpr int kEager = 32;    // measurements taken one per launch; then one in kEvery launches
+        static constexpr int kEvery = 8;
+        bool on = true;                      // SDDC_DDC_PARAM_FS_ADAPTIVE_SPLIT
+        sddc::FsSplitController ctl;
+        std::vector<float> forced;           // sddc_ddc_internal_fs_set_shares
+        unsigned *h_ring = nullptr, *d_ring = nullptr;   // [kRing][kFsShareMaxG][4]
+        bool ring_failed = false;
+        struct Pending {
+            unsigned tag = 0u;
+            int G = 0, ns = 0;
+            bool live = false, tainted = false;
+            std::vector<int> n;              // frames per workgroup of that launch
+        } pend[kRing];
+        int next = 0, last_pending = -1;
+        unsigned seq = 0u;
+        sddc::FsShares tab = {};             // the current table, its batch size and frames per workgroup
+        std::vector<int> tab_n, base_n;
+        int tab_ns = -1, base_ns = -1;
+        hipStream_t cur_s = nullptr, last_s = nullptr;
+        bool have_last = false;
+        int taint_left = 0;
+        long launches = 0, skipped = 0;
+        int last_table = 0, last_logged = 0; // the last d = 0 launch: took a table / was measured
+    } fsa;
     bool q_used[kQueueSlots] = {};
     bool q_dirty[kQueueSlots] = {};
     Readers readers;
@@ -467,6 +505,7 @@ int sddc_ddc_destroy(sddc_ddc_t *h)
         if (h->d_pq) (void)hipFree(h->d_pq);
         if (h->d_fs) (void)hipFree(h->d_fs);
         if (h->d_queue) (void)hipFree(h->d_queue);
+        if (h->fsa.h_ring) (void)hipHostFree(h->fsa.h_ring);   // its writers were waited for above
         h->readers.clear();
         h->ch_readers.clear();
         for (int i = 0; i < sddc_ddc::kNcoSlots; i++) {
@@ -658,6 +697,107 @@ static hipError_t order_after_build(sddc_ddc_t *h, hipStream_t built, hipStream_
     return h->readers.order_after(built, s);
 }
 
+// The adaptive split's hook of a d = 0 launch (ddc_kernels.h FsSched::adapt), under h->mu.
+static bool fs_adapt_prepare(void *ctx, int G, int ns, const sddc::FsShares **tab, unsigned **tlog, unsigned *tag)
+{
+    using sddc::kFsShareMaxG;
+    sddc_ddc_t *h = static_cast<sddc_ddc_t *>(ctx);
+    sddc_ddc::FsAdapt &a = h->fsa;
+    const bool want_forced = (int)a.forced.size() == G;
+    if (!a.on && !want_forced) return false;
+    if (a.ctl.groups() != G) a.ctl.reset(G, sddc::kFsSlotWeights);
+    if (want_forced && !a.ctl.forced()) a.ctl.load(a.forced.data(), G);
+    if (!want_forced && a.ctl.forced()) a.ctl.unload();
+    a.ctl.set_frames(ns);
+    const bool learn = a.on && !a.ctl.forced();
+    bool changed = false;
+    if (learn && a.h_ring) {
+        // pick up what has completed, oldest first
+        const bool take = a.ctl.measured() < sddc_ddc::FsAdapt::kEager || a.launches % sddc_ddc::FsAdapt::kEvery == 0;
+        for (int k = 0; k < sddc_ddc::FsAdapt::kRing && take; k++) {
+            auto &p = a.pend[(a.next + k) % sddc_ddc::FsAdapt::kRing];
+            if (!p.live) continue;
+            const volatile unsigned *e = a.h_ring + (size_t)((a.next + k) % sddc_ddc::FsAdapt::kRing) * kFsShareMaxG * 4;
+            bool done = true;
+            for (int w = 0; w < p.G && done; w++)
+                done = e[4 * w + 2] == p.tag && (e[4 * w] ^ e[4 * w + 1] ^ p.tag) == e[4 * w + 3];
+            if (!done) continue;
+            p.live = false;
+            if (p.tainted || p.G != G || p.ns != ns) {
+                a.skipped++;
+                continue;
+            }
+            uint32_t st[kFsShareMaxG], en[kFsShareMaxG];
+            for (int w = 0; w < G; w++) {
+                st[w] = e[4 * w];
+                en[w] = e[4 * w + 1];
+            }
+            // read while the next launch of the slot cannot have started (it is enqueued below at
+            // the earliest); a torn copy would fail nothing worse than the controller's bounds
+            if (a.ctl.update(p.n.data(), st, en)) changed = true;
+            else a.skipped++;
+        }
+    }
+    a.launches++;
+    const std::vector<int> *n = nullptr;
+    if (a.ctl.warm()) {
+        if (changed || a.tab_ns != ns) {
+            a.tab_n.resize((size_t)G);
+            a.ctl.table(ns, &a.tab, a.tab_n.data());
+            a.tab_ns = ns;
+        }
+        *tab = &a.tab;
+        n = &a.tab_n;
+        a.last_table = 1;
+    } else {
+        if (a.base_ns != ns || (int)a.base_n.size() != G) {
+            a.base_n.resize((size_t)G);
+            for (int w = 0; w < G; w++)
+                a.base_n[(size_t)w] = sddc::fs_slot_split_host(ns, G, w + 1, sddc::kFsSlotWeights) -
+                                      sddc::fs_slot_split_host(ns, G, w, sddc::kFsSlotWeights);
+            a.base_ns = ns;
+        }
+        *tab = nullptr;
+        n = &a.base_n;
+    }
+    *tlog = nullptr;
+    *tag = 0u;
+    if (!learn) return true;
+    if (!a.h_ring && !a.ring_failed) {
+        const size_t bytes = (size_t)sddc_ddc::FsAdapt::kRing * kFsShareMaxG * 4 * sizeof(unsigned);
+        void *hp = nullptr, *dp = nullptr;
+        if (hipHostMalloc(&hp, bytes, hipHostMallocMapped) == hipSuccess) {
+            if (hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess) {
+                std::memset(hp, 0, bytes);
+                a.h_ring = static_cast<unsigned *>(hp);
+                a.d_ring = static_cast<unsigned *>(dp);
+            } else {
+                (void)hipHostFree(hp);
+            }
+        }
+        if (!a.h_ring) {
+            a.ring_failed = true;   // no measurements: the launches keep the built-in split
+            (void)hipGetLastError();
+        }
+    }
+    if (!a.h_ring) return true;
+    const int i = a.next;
+    a.next = (i + 1) % sddc_ddc::FsAdapt::kRing;
+    if (++a.seq == 0u) a.seq = 1u;
+    auto &p = a.pend[i];
+    p.tag = a.seq;
+    p.G = G;
+    p.ns = ns;
+    p.live = true;
+    p.tainted = a.taint_left > 0;
+    p.n = *n;
+    a.last_pending = i;
+    a.last_logged = 1;
+    *tlog = a.d_ring + (size_t)i * kFsShareMaxG * 4;
+    *tag = p.tag;
+    return true;
+}
+
 static hipError_t launch_single_impl(sddc_ddc_t *h, const int16_t *d_in, int nblk, void *d_out, hipStream_t s);
 
 static hipError_t launch_single(sddc_ddc_t *h, const int16_t *d_in, int nblk, void *d_out, hipStream_t s)
@@ -669,6 +809,20 @@ static hipError_t launch_single(sddc_ddc_t *h, const int16_t *d_in, int nblk, vo
 
 static hipError_t launch_single_impl(sddc_ddc_t *h, const int16_t *d_in, int nblk, void *d_out, hipStream_t s)
 {
+    {
+        // a launch on another stream than the handle's last one may overlap it (and what follows)
+        sddc_ddc::FsAdapt &a = h->fsa;
+        if (a.have_last && a.last_s != s) {
+            a.taint_left = sddc_ddc::FsAdapt::kTaint + 1;
+            if (a.last_pending >= 0) a.pend[a.last_pending].tainted = true;
+        } else if (a.taint_left > 0) {
+            a.taint_left--;
+        }
+        a.last_s = s;
+        a.have_last = true;
+        a.last_pending = -1;
+        a.last_table = a.last_logged = 0;
+    }
     const bool nco = h->nco_fc != 0.f;
     if (nco) {
         hipError_t e = stage_nco(h, nblk, s);
@@ -697,6 +851,8 @@ static hipError_t launch_single_impl(sddc_ddc_t *h, const int16_t *d_in, int nbl
         int qi = -1;
         hipError_t e = hipSuccess;
         if (h->fs_sched.sched != 0 && (e = next_queue_slot(h, s, &wq, &qi)) != hipSuccess) return e;
+        h->fs_sched.adapt = fs_adapt_prepare;
+        h->fs_sched.adapt_ctx = h;
         e = sddc::launch_frames_fs(h->tables, d_in, nblk, d_out, pqf, fsl, h->tunebin, h->lsb, h->rand,
                                    h->out_fmt == SDDC_DDC_FMT_CS16, h->cs16_scale, nco_starts, nco_trig, wq,
                                    h->fs_sched, h->device, s);
@@ -847,6 +1003,9 @@ int sddc_ddc_internal_set_param(sddc_ddc_t *h, int param, int value)
         if (value < 0 || value > 1024) return fail(SDDC_ERR_ARG, "public frames %d outside 0..1024", value);
         h->fs_sched.pub = value;
         return SDDC_OK;
+    case SDDC_DDC_PARAM_FS_ADAPTIVE_SPLIT:
+        h->fsa.on = value != 0;
+        return SDDC_OK;
     case SDDC_DDC_PARAM_CH_NCO_RUN_BLOCKS:
         if (value < 0 || value > SDDC_DDC_MAX_BLOCKS)
             return fail(SDDC_ERR_ARG, "run blocks %d outside 0..%d", value, SDDC_DDC_MAX_BLOCKS);
@@ -855,6 +1014,98 @@ int sddc_ddc_internal_set_param(sddc_ddc_t *h, int param, int value)
     default:
         return fail(SDDC_ERR_ARG, "unknown parameter %d", param);
     }
+}
+
+/* internal: a given table of relative shares for the d = 0 kernel's full-residency launches
+ * (n = the grid, 4 x CUs), used as it is until n = 0 clears it; no measurements are taken meanwhile */
+int sddc_ddc_internal_fs_set_shares(sddc_ddc_t *h, const float *shares, int n)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    if (n < 0 || n > sddc::kFsShareMaxG || (n > 0 && !shares)) return fail(SDDC_ERR_ARG, "shares: n %d outside 0..%d", n, sddc::kFsShareMaxG);
+    double sum = 0.0;
+    for (int w = 0; w < n; w++) {
+        if (!(shares[w] >= 0.f) || !std::isfinite(shares[w])) return fail(SDDC_ERR_ARG, "share %d is negative or not finite", w);
+        sum += shares[w];
+    }
+    if (n > 0 && !(sum > 0.0)) return fail(SDDC_ERR_ARG, "shares: all zero");
+    std::lock_guard<std::mutex> lk(h->mu);
+    h->fsa.forced.assign(shares, shares + n);
+    if (h->fsa.ctl.forced()) h->fsa.ctl.unload();
+    h->fsa.tab_ns = -1;
+    return SDDC_OK;
+}
+
+/* internal: the adaptive split's state: info = {grid of the controller, measurements used,
+ * measurements skipped, the last d = 0 launch took a share table, the last d = 0 launch was
+ * measured}; counts (ncounts >= grid, or null) receives the current table's frames per workgroup
+ * when it has one.  Returns the number of counts written. */
+int sddc_ddc_internal_fs_split_state(sddc_ddc_t *h, long *info, int *counts, int ncounts)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    const sddc_ddc::FsAdapt &a = h->fsa;
+    if (info) {
+        info[0] = a.ctl.groups();
+        info[1] = a.ctl.measured();
+        info[2] = a.skipped;
+        info[3] = a.last_table;
+        info[4] = a.last_logged;
+    }
+    int nw = 0;
+    if (counts && a.tab_ns >= 0 && ncounts >= (int)a.tab_n.size()) {
+        nw = (int)a.tab_n.size();
+        std::copy(a.tab_n.begin(), a.tab_n.end(), counts);
+    }
+    return nw;
+}
+
+/* internal: the controller alone, without a handle or a device (tests/test_adaptive_split.py) */
+void *sddc_fs_split_create(int G, unsigned slot_weights)
+{
+    if (G < 1 || G > sddc::kFsShareMaxG) return nullptr;
+    auto *c = new (std::nothrow) sddc::FsSplitController;
+    if (c) c->reset(G, slot_weights);
+    return c;
+}
+void sddc_fs_split_destroy(void *c) { delete static_cast<sddc::FsSplitController *>(c); }
+int sddc_fs_split_load(void *c, const float *shares, int n)
+{
+    auto *k = static_cast<sddc::FsSplitController *>(c);
+    if (n == 0) {
+        k->unload();
+        return 0;
+    }
+    return k->load(shares, n) ? 0 : -1;
+}
+/* the table of a launch of ns frames: p (G + 1 entries: the 15-bit shares, then 32768) and the
+ * first frame of every workgroup as the kernel computes it (first: G + 1 entries, the last ns) */
+int sddc_fs_split_table(void *c, int ns, unsigned *p, int *first)
+{
+    auto *k = static_cast<sddc::FsSplitController *>(c);
+    const int G = k->groups();
+    if (ns < 0) return -1;
+    sddc::FsShares t;
+    std::vector<int> n((size_t)G);
+    k->table(ns, &t, n.data());
+    if (!sddc::fs_shares_valid(t, G)) return -2;
+    for (int w = 0; w <= G; w++) {
+        if (p) p[w] = w < G ? sddc::fs_share_get(t, w) : sddc::kFsShareOne;
+        if (first) first[w] = sddc::fs_share_start(ns, G, w, t);
+    }
+    return 0;
+}
+int sddc_fs_split_update(void *c, const int *n, const unsigned *start, const unsigned *end)
+{
+    return static_cast<sddc::FsSplitController *>(c)->update(n, start, end) ? 1 : 0;
+}
+int sddc_fs_split_model(void *c, double *cost, double *offset)
+{
+    auto *k = static_cast<sddc::FsSplitController *>(c);
+    for (int w = 0; w < k->groups(); w++) {
+        if (cost) cost[w] = k->cost()[(size_t)w];
+        if (offset) offset[w] = k->offset()[(size_t)w];
+    }
+    return k->groups();
 }
 
 static int check_process_args(sddc_ddc_t *h, const int16_t *in, int nblk, const void *out)

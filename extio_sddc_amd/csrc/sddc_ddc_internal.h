@@ -32,15 +32,35 @@ extern "C" {
 #define SDDC_DDC_PARAM_FS_ZERO_ROWS 7
 /* SDDC_DDC_PARAM_FS_SLOT_WEIGHTS: the d = 0 kernel's slot weights of the static split, four
  * bytes w0 | w1 << 8 | w2 << 16 | w3 << 24 (CU slot 0 in the low byte, each 1..127); 0: the
- * built-in kFsSlotWeights (A/B of the weights). */
+ * built-in kFsSlotWeights (A/B of the weights).  Launches with explicit weights use them as they
+ * are: the adaptive split (SDDC_DDC_PARAM_FS_ADAPTIVE_SPLIT) neither changes nor measures them. */
 #define SDDC_DDC_PARAM_FS_SLOT_WEIGHTS 8
 /* SDDC_DDC_PARAM_CH_NCO_RUN_BLOCKS = n > 0: with the per-channel NCO on, process_channels_device
  * cuts a call into runs of at most n input blocks (a chain launch + a channels launch each); 0
  * (default): as many blocks as the lane-start table's byte cap holds (ddc_runtime.cpp
  * kChNcoTableCap), which bounds n > 0 too.  The cut changes no output bit (tests). */
 #define SDDC_DDC_PARAM_CH_NCO_RUN_BLOCKS 9
+/* SDDC_DDC_PARAM_FS_ADAPTIVE_SPLIT != 0 (default 1): full-residency launches of the d = 0 kernel's
+ * static schedule with the built-in slot weights take their per-workgroup frame split from the
+ * handle's controller, which learns it from the workgroups' measured start and end times
+ * (fs_split_controller.hpp); 0: the built-in slot-weighted split, nothing measured. */
+#define SDDC_DDC_PARAM_FS_ADAPTIVE_SPLIT 10
 
 int sddc_ddc_internal_set_param(sddc_ddc_t *h, int param, int value);
+/* A given table of n relative shares (n = the d = 0 kernel's full-residency grid, 4 x CUs) used as
+ * it is, without clamps or measurements, until n = 0 clears it (tests). */
+int sddc_ddc_internal_fs_set_shares(sddc_ddc_t *h, const float *shares, int n);
+/* The adaptive split's state: info[5] = {the controller's grid, measurements used, measurements
+ * skipped, the last d = 0 launch took a share table, the last d = 0 launch was measured}; counts
+ * receives the current table's frames per workgroup.  Returns the number of counts written. */
+int sddc_ddc_internal_fs_split_state(sddc_ddc_t *h, long *info, int *counts, int ncounts);
+/* The controller alone (no handle, no device): tests/test_adaptive_split.py. */
+void *sddc_fs_split_create(int G, unsigned slot_weights);
+void sddc_fs_split_destroy(void *c);
+int sddc_fs_split_load(void *c, const float *shares, int n);
+int sddc_fs_split_table(void *c, int ns, unsigned *p, int *first);
+int sddc_fs_split_update(void *c, const int *n, const unsigned *start, const unsigned *end);
+int sddc_fs_split_model(void *c, double *cost, double *offset);
 /* Diagnostic stamp buffers of -DSDDC_STAMPS builds (tools/fs_stamps.py); -1 in product builds. */
 int sddc_ddc_internal_fs_stamps(unsigned *host, int nwords, int *words_per_wave);
 int sddc_ddc_internal_p_stamps(unsigned *host, int nwords, int *words_per_wave);

@@ -37,6 +37,9 @@ def main():
     ap.add_argument("--input", choices=["rand", "bench", "zeros"], default="rand",
                     help="rand: uniform int16; bench: bench.py's tone mix + noise (its make_input)")
     ap.add_argument("--heat-s", type=float, default=2.0)
+    ap.add_argument("--warm", type=int, default=0,
+                    help="untimed launches of every library before its timed rounds, ten at a time with a synchronise "
+                         "after each ten (bench.py's warm-up: what the adaptive frame split learns from)")
     args = ap.parse_args()
 
     import torch
@@ -124,6 +127,12 @@ def main():
             assert rc == 0, L.sddc_ddc_last_error()
             torch.cuda.synchronize()
             unwritten.append(int(torch.isnan(outs[i]).sum().item()))
+        for L, h, o in zip(libs, handles, outs):
+            for k in range(args.warm if not args.channels else 0):
+                assert L.sddc_ddc_process_device(h, d_in.data_ptr(), nblk, o.data_ptr(), s) == 0
+                if k % 10 == 9:
+                    torch.cuda.synchronize()
+        torch.cuda.synchronize()
         for rnd in range(args.rounds + 1):
             for i, (L, h) in enumerate(zip(libs, handles)):
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -147,7 +156,8 @@ def main():
             frac = nblk * 65536 * (2 + 4 * nch / (1 << d)) / (med * 1e-3) / 8e12
             res[f"d{d}:{os.path.basename(p)}#{i}"] = {"median_ms": med, "min_ms": ts[0], "max_ms": ts[-1], "GSps": gs,
                                                   "hbm_frac": frac, "channel_nco": nco_on[i],
-                                                  "maxrel_vs_first": diff, "unwritten_floats": unwritten[i]}
+                                                  "maxrel_vs_first": diff, "unwritten_floats": unwritten[i],
+                                                  "rounds_ms": times[i]}
             print(f"d={d} {os.path.basename(p):28s} median {med:.3f} ms min {ts[0]:.3f} max {ts[-1]:.3f}  {gs:7.1f} GS/s  "
                   f"roofline {frac*100:5.1f}%  maxrel vs first {diff:.2e}"
                   + (f"  INCOMPLETE: {unwritten[i]} floats unwritten" if unwritten[i] else ""), flush=True)
