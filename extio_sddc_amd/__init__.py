@@ -6,7 +6,10 @@ class in include/fft_mt_r2iq.h; this package is its Python host mirror (ctypes).
 from ._lib import BACKEND_CPU, BACKEND_HIP, DEVICE_CPU, DDCError, build, load  # noqa: F401
 from .r2iq import (BBRF103_GAINFACTOR, BLOCK, FRAMES, HALF_FFT, NDEC, OUT_BLOCK,  # noqa: F401
                    R2iq, channel_tuning, device_count, filter_response, filter_taps, kaiser, output_samples)
+from .r2iq import (FFTN, SPECTRUM_BINS, WINDOW_BLACKMAN_HARRIS, WINDOW_HANN, WINDOW_RECT,  # noqa: F401
+                   psd_to_dbfs, spectrum_window)
 
 __all__ = ["R2iq", "DDCError", "DEVICE_CPU", "BACKEND_CPU", "BACKEND_HIP", "build", "load", "kaiser", "filter_taps", "filter_response",
            "channel_tuning", "device_count", "output_samples", "HALF_FFT", "BLOCK", "FRAMES", "NDEC", "OUT_BLOCK",
-           "BBRF103_GAINFACTOR"]
+           "BBRF103_GAINFACTOR", "spectrum_window", "psd_to_dbfs", "FFTN", "SPECTRUM_BINS", "WINDOW_RECT", "WINDOW_HANN",
+           "WINDOW_BLACKMAN_HARRIS"]

@@ -222,5 +222,57 @@ void R2iq::process(const int16_t *const *blocks, int nblk, void *out, const Para
     }
 }
 
+// The averaged power spectrum (sddc_ddc_spectrum_host on a CPU handle): per frame the windowed
+// samples as x[2j] + i x[2j+1] through the forward plan, the plain r2c split
+//   A = Zk + conj Zc, B = -i W^k (Zk - conj Zc), |X[k]|^2 = |A + B|^2 / 4, |X[4096 - k]|^2 = |A - B|^2 / 4
+// and a float sum per bin over the row's frames in frame order, scaled once at the end.
+void R2iq::spectrum(const int16_t *in, int nblk, int bpr, const float *w, float scale, bool rand, float *psd)
+{
+    Buf &B = *b_;
+    if (sw_.empty()) {
+        sw_.resize(2 * (size_t)(kHalf / 2 + 1));
+        for (int k = 0; k <= kHalf / 2; k++) {
+            const double a = -2.0 * M_PI * k / (2.0 * kHalf);
+            sw_[2 * (size_t)k] = (float)std::cos(a);
+            sw_[2 * (size_t)k + 1] = (float)std::sin(a);
+        }
+    }
+    std::vector<float> acc(kHalf);
+    const float s4 = 0.25f * scale;
+    for (int row = 0; row < nblk / bpr; row++) {
+        std::fill(acc.begin(), acc.end(), 0.f);
+        for (int f = 0; f < bpr * kFrames; f++) {
+            const int16_t *x = in + (size_t)(row * bpr + f / kFrames) * kBlock + (size_t)(f % kFrames) * kHop;
+            float *re = B.ar.p, *im = B.ai.p;
+            for (int j = 0; j < kHalf; j++) {
+                int a = x[2 * j], b = x[2 * j + 1];
+                if (rand) {   // fft_mt_r2iq.h:36-51: an odd sample is XORed with 0xFFFE (its negation)
+                    a = (a & 1) ? -a : a;
+                    b = (b & 1) ? -b : b;
+                }
+                re[j] = w ? w[2 * j] * (float)a : (float)a;
+                im[j] = w ? w[2 * j + 1] * (float)b : (float)b;
+            }
+            if (fwd_.forward(B.ar.p, B.ai.p, B.br.p, B.bi.p)) {
+                re = B.br.p;
+                im = B.bi.p;
+            }
+            // k = 0: X[0] = Re Z0 + Im Z0; k = 2048: X = conj Z[2048]
+            acc[0] += 4.f * (re[0] + im[0]) * (re[0] + im[0]);
+            acc[kHalf / 2] += 4.f * (re[kHalf / 2] * re[kHalf / 2] + im[kHalf / 2] * im[kHalf / 2]);
+            for (int k = 1; k < kHalf / 2; k++) {
+                const float zkx = re[k], zky = im[k], zcx = re[kHalf - k], zcy = im[kHalf - k];
+                const float ax = zkx + zcx, ay = zky - zcy, dx = zkx - zcx, dy = zky + zcy;
+                const float wx = sw_[2 * (size_t)k], wy = sw_[2 * (size_t)k + 1];
+                const float bx = wx * dy + wy * dx, by = -(wx * dx - wy * dy);   // B = -i W D
+                const float px = ax + bx, py = ay + by, mx = ax - bx, my = ay - by;
+                acc[k] += px * px + py * py;
+                acc[kHalf - k] += mx * mx + my * my;
+            }
+        }
+        for (int k = 0; k < kHalf; k++) psd[(size_t)row * kHalf + k] = acc[k] * s4;
+    }
+}
+
 }  // namespace cpu
 }  // namespace sddc

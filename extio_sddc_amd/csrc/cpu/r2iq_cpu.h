@@ -56,6 +56,11 @@ public:
     // nblk blocks, block i at blocks[i]; writes nblk * (32768 >> d) complex samples to out
     // (CF32: float (I, Q); CS16: int16 (I, Q)) and keeps the last 4096 input samples
     void process(const int16_t *const *blocks, int nblk, void *out, const Params &p);
+    // The averaged power spectrum of in = [history 4096 | nblk blocks] (sddc_ddc.h,
+    // sddc_ddc_spectrum_host): psd[nblk / bpr][4096], row r = scale x the sum of |X_f[k]|^2 over the
+    // 11 bpr frames of blocks r bpr .. r bpr + bpr - 1 in frame order; w = the 8192-point window
+    // (null: rectangular).  Stateless: it neither reads nor changes the kept history.
+    void spectrum(const int16_t *in, int nblk, int bpr, const float *w, float scale, bool rand, float *psd);
 
 private:
     struct Buf;
@@ -68,6 +73,7 @@ private:
     std::vector<std::complex<double>> H_;           // [7][4096]
     int pq_d_ = -1, pq_tb_ = -1;
     int lo_ = 0, hi_ = 0;                           // valid m ranges of the (P, Q) table
+    std::vector<float> sw_;                         // spectrum(): W_8192^k, k <= 2048, as (cos, sin)
 };
 
 }  // namespace cpu

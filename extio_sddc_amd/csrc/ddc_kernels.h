@@ -166,6 +166,18 @@ hipError_t launch_channels_p(const KernelTables &t, int d, const int16_t *d_in, 
 // host: the compact windows of every chunk; false if a chunk's window does not fit
 bool channel_windows(int d, const int *tunebins, int nch, int2 *windows);
 
+// Wideband averaged power spectrum (ddc_spectrum.hip, sddc_ddc_spectrum_device): persistent
+// workgroups, one input block (11 frames of the DDC's schedule) per work item.  d_out receives
+// scale x the sum of 4 |X_f[k]|^2 over each block's frames, nblk rows of 4096 floats (4-byte
+// aligned): the finished rows when a row is one block, else the partial rows (scale = 1) that
+// launch_spectrum_reduce adds per row, in block order, and scales.  d_window: 8192 floats, or
+// nullptr for the rectangular window (no multiply).  max_wgs > 0 caps the grid (tests).
+hipError_t launch_spectrum(const KernelTables &t, const int16_t *d_in, int nblk, float *d_out, const float *d_window,
+                           float scale, int rand, int max_wgs, int device, hipStream_t s);
+// d_partial: rows x blocks_per_row x 4096 floats, 16-byte aligned; d_psd: rows x 4096, 4-byte aligned
+hipError_t launch_spectrum_reduce(const float *d_partial, int rows, int blocks_per_row, float scale, float *d_psd,
+                                  hipStream_t s);
+
 // batched FFTs (fft_batch.hip, include/sddc_fft.h); fft_prepare fills the device's twiddle
 // table once (synchronises s the first time)
 hipError_t fft_prepare(hipStream_t s);

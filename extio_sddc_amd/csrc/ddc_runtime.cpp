@@ -270,6 +270,22 @@ struct sddc_ddc {
     // history to start the next host-path call from (sddc_ddc_set_history)
     std::vector<int16_t> hist_override;
 
+    // wideband spectrum (sddc_ddc_spectrum_*): the window (empty = rectangular) with its sum, its
+    // device copy, the partial rows [blocks][4096] of calls with more than one block per row
+    // (grown on demand) and the host call's device buffers.  sp_readers holds the streams of the
+    // spectrum launches: a launch that uses the partial rows waits for the other streams' last
+    // launches, a change of the window or a regrowth for all of them.
+    std::vector<float> sp_win;
+    double sp_wsum = (double)SDDC_DDC_FFTN;
+    float *d_sp_win = nullptr;             // [8192]
+    float *d_sp_partial = nullptr;
+    size_t sp_partial_cap = 0;             // blocks
+    int16_t *d_sp_in = nullptr;            // spectrum_host: [4096 + sp_host_cap * 65536]
+    float *d_sp_out = nullptr;             // spectrum_host: [sp_host_cap][4096]
+    size_t sp_host_cap = 0;                // blocks
+    Readers sp_readers;
+    int sp_max_wgs = 0;                    // SDDC_DDC_PARAM_SPECTRUM_MAX_WGS
+
     // CPU handle (device SDDC_DDC_DEVICE_CPU): the AVX2 backend; no HIP object above exists
     std::unique_ptr<sddc::cpu::R2iq> cpu;
 
@@ -483,6 +499,7 @@ int sddc_ddc_destroy(sddc_ddc_t *h)
         // launches on the callers' streams may still read the tables below: wait for them first
         (void)h->readers.sync();
         (void)h->ch_readers.sync();
+        (void)h->sp_readers.sync();
         if (h->d_tables) (void)hipFree(h->d_tables);
         for (auto &sl : h->hs) {
             if (sl.d_in) (void)hipFree(sl.d_in);
@@ -505,6 +522,11 @@ int sddc_ddc_destroy(sddc_ddc_t *h)
         if (h->d_pq) (void)hipFree(h->d_pq);
         if (h->d_fs) (void)hipFree(h->d_fs);
         if (h->d_queue) (void)hipFree(h->d_queue);
+        if (h->d_sp_win) (void)hipFree(h->d_sp_win);
+        if (h->d_sp_partial) (void)hipFree(h->d_sp_partial);
+        if (h->d_sp_in) (void)hipFree(h->d_sp_in);
+        if (h->d_sp_out) (void)hipFree(h->d_sp_out);
+        h->sp_readers.clear();
         if (h->fsa.h_ring) (void)hipHostFree(h->fsa.h_ring);   // its writers were waited for above
         h->readers.clear();
         h->ch_readers.clear();
@@ -1011,6 +1033,10 @@ int sddc_ddc_internal_set_param(sddc_ddc_t *h, int param, int value)
             return fail(SDDC_ERR_ARG, "run blocks %d outside 0..%d", value, SDDC_DDC_MAX_BLOCKS);
         h->chnco_run_blocks = value;
         return SDDC_OK;
+    case SDDC_DDC_PARAM_SPECTRUM_MAX_WGS:
+        if (value < 0) return fail(SDDC_ERR_ARG, "spectrum workgroup cap %d is negative", value);
+        h->sp_max_wgs = value;
+        return SDDC_OK;
     default:
         return fail(SDDC_ERR_ARG, "unknown parameter %d", param);
     }
@@ -1245,6 +1271,159 @@ int sddc_ddc_process_channels_device(sddc_ddc_t *h, const int16_t *d_in, int nbl
         HIP_TRY(er);
     }
     return SDDC_OK;
+}
+
+/* ---- wideband averaged power spectrum --------------------------------------------------- */
+int sddc_ddc_spectrum_window(int kind, float *w)
+{
+    if (!w) return fail(SDDC_ERR_ARG, "spectrum_window: null array");
+    // periodic (DFT-even) cosine-sum windows, evaluated in double and rounded once
+    static const double kRect[] = {1.0}, kHann[] = {0.5, 0.5}, kBh[] = {0.35875, 0.48829, 0.14128, 0.01168};
+    const double *a;
+    int na;
+    switch (kind) {
+    case SDDC_DDC_WINDOW_RECT: a = kRect, na = 1; break;
+    case SDDC_DDC_WINDOW_HANN: a = kHann, na = 2; break;
+    case SDDC_DDC_WINDOW_BLACKMAN_HARRIS: a = kBh, na = 4; break;
+    default: return fail(SDDC_ERR_ARG, "spectrum_window: unknown window %d", kind);
+    }
+    for (int j = 0; j < SDDC_DDC_FFTN; j++) {
+        double v = 0.0;
+        for (int m = 0; m < na; m++) v += ((m & 1) ? -a[m] : a[m]) * std::cos(2.0 * M_PI * m * j / SDDC_DDC_FFTN);
+        w[j] = (float)v;
+    }
+    return SDDC_OK;
+}
+
+int sddc_ddc_set_spectrum_window(sddc_ddc_t *h, const float *w)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    double sum = (double)SDDC_DDC_FFTN;
+    if (w) {
+        sum = 0.0;
+        for (int j = 0; j < SDDC_DDC_FFTN; j++) {
+            if (!std::isfinite(w[j])) return fail(SDDC_ERR_ARG, "spectrum window: value %d is not finite", j);
+            sum += w[j];
+        }
+        if (!(sum > 0.0)) return fail(SDDC_ERR_ARG, "spectrum window: the sum of the window must be > 0");
+    }
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (w && !h->cpu) {
+        DeviceGuard g(h->device);
+        HIP_TRY(g.err);
+        HIP_TRY(h->sp_readers.sync());   // earlier launches, on any stream, may still read the device copy
+        if (!h->d_sp_win) HIP_TRY(hipMalloc(&h->d_sp_win, SDDC_DDC_FFTN * sizeof(float)));
+        h->sp_win.clear();               // a failed upload leaves the rectangular window
+        h->sp_wsum = (double)SDDC_DDC_FFTN;
+        HIP_TRY(hipMemcpy(h->d_sp_win, w, SDDC_DDC_FFTN * sizeof(float), hipMemcpyHostToDevice));
+    }
+    if (w) h->sp_win.assign(w, w + SDDC_DDC_FFTN);
+    else h->sp_win.clear();
+    h->sp_wsum = sum;
+    return SDDC_OK;
+}
+
+static int check_spectrum_args(const int16_t *in, int nblk, int bpr, const float *psd)
+{
+    if (nblk <= 0 || nblk > SDDC_DDC_MAX_BLOCKS)
+        return fail(SDDC_ERR_ARG, "nblk must be in 1..%d (got %d)", SDDC_DDC_MAX_BLOCKS, nblk);
+    if (bpr < 1 || nblk % bpr != 0)
+        return fail(SDDC_ERR_ARG, "blocks_per_row must be >= 1 and divide nblk (got %d, nblk %d)", bpr, nblk);
+    if (!in || !psd) return fail(SDDC_ERR_ARG, "null buffer");
+    if (((uintptr_t)in & 3) != 0) return fail(SDDC_ERR_ARG, "input must be 4-byte aligned");
+    if (((uintptr_t)psd & 3) != 0) return fail(SDDC_ERR_ARG, "psd must be 4-byte aligned");
+    return SDDC_OK;
+}
+
+// 1 / (11 bpr (sum w)^2), in double
+static double spectrum_scale(const sddc_ddc_t *h, int bpr)
+{
+    return 1.0 / ((double)SDDC_DDC_FRAMES * (double)bpr * h->sp_wsum * h->sp_wsum);
+}
+
+// the spectrum launches of one call on s (under h->mu)
+static int spectrum_launch(sddc_ddc_t *h, const int16_t *d_in, int nblk, int bpr, float *d_psd, hipStream_t s)
+{
+    const float *win = h->sp_win.empty() ? nullptr : h->d_sp_win;
+    // the kernel sums 4 |X|^2 (it leaves out the split's 1/2)
+    const float scale = (float)(0.25 * spectrum_scale(h, bpr));
+    if (bpr == 1) {
+        HIP_TRY(sddc::launch_spectrum(h->tables, d_in, nblk, d_psd, win, scale, h->rand, h->sp_max_wgs, h->device, s));
+        HIP_TRY(h->sp_readers.record(s));
+        return SDDC_OK;
+    }
+    if ((size_t)nblk > h->sp_partial_cap) {   // earlier launches may still use the old rows
+        HIP_TRY(h->sp_readers.sync());
+        if (h->d_sp_partial) (void)hipFree(h->d_sp_partial);
+        h->d_sp_partial = nullptr;
+        h->sp_partial_cap = 0;
+        HIP_TRY(hipMalloc(&h->d_sp_partial, (size_t)nblk * SDDC_DDC_SPECTRUM_BINS * sizeof(float)));
+        h->sp_partial_cap = (size_t)nblk;
+    } else {
+        // the partial rows are per handle: this launch must not overlap one on another stream
+        HIP_TRY(h->sp_readers.order_before(s));
+    }
+    hipError_t e = sddc::launch_spectrum(h->tables, d_in, nblk, h->d_sp_partial, win, 1.f, h->rand, h->sp_max_wgs,
+                                         h->device, s);
+    if (e == hipSuccess) e = sddc::launch_spectrum_reduce(h->d_sp_partial, nblk / bpr, bpr, scale, d_psd, s);
+    const hipError_t er = h->sp_readers.record(s);   // whatever was enqueued stays ordered
+    HIP_TRY(e);
+    HIP_TRY(er);
+    return SDDC_OK;
+}
+
+int sddc_ddc_spectrum_device(sddc_ddc_t *h, const int16_t *d_in, int nblk, int blocks_per_row, float *d_psd,
+                             void *hip_stream)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(h->mu);   // the call reads rand and the window: one consistent set
+    if (h->cpu) return fail(SDDC_ERR_STATE, "spectrum_device: a CPU handle has no device path");
+    if (int rc = check_spectrum_args(d_in, nblk, blocks_per_row, d_psd)) return rc;
+    DeviceGuard g(h->device);
+    HIP_TRY(g.err);
+    return spectrum_launch(h, d_in, nblk, blocks_per_row, d_psd, (hipStream_t)hip_stream);
+}
+
+int sddc_ddc_spectrum_host(sddc_ddc_t *h, const int16_t *in, int nblk, int blocks_per_row, float *psd)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (int rc = check_spectrum_args(in, nblk, blocks_per_row, psd)) return rc;
+    if (h->cpu) {
+        try {
+            h->cpu->spectrum(in, nblk, blocks_per_row, h->sp_win.empty() ? nullptr : h->sp_win.data(),
+                             (float)spectrum_scale(h, blocks_per_row), h->rand != 0, psd);
+        } catch (const std::exception &ex) {
+            return fail(SDDC_ERR_NOMEM, "cpu backend: %s", ex.what());
+        }
+        return SDDC_OK;
+    }
+    DeviceGuard g(h->device);
+    HIP_TRY(g.err);
+    if ((size_t)nblk > h->sp_host_cap) {   // the earlier host calls were synchronous: nothing reads the old buffers
+        if (h->d_sp_in) (void)hipFree(h->d_sp_in);
+        if (h->d_sp_out) (void)hipFree(h->d_sp_out);
+        h->d_sp_in = nullptr;
+        h->d_sp_out = nullptr;
+        h->sp_host_cap = 0;
+        if (hipMalloc(&h->d_sp_in, (kHistory + (size_t)nblk * kBlock) * sizeof(int16_t)) != hipSuccess ||
+            hipMalloc(&h->d_sp_out, (size_t)nblk * SDDC_DDC_SPECTRUM_BINS * sizeof(float)) != hipSuccess) {
+            (void)hipGetLastError();
+            if (h->d_sp_in) (void)hipFree(h->d_sp_in);
+            h->d_sp_in = nullptr;
+            return fail(SDDC_ERR_NOMEM, "spectrum_host: no device memory for %d blocks", nblk);
+        }
+        h->sp_host_cap = (size_t)nblk;
+    }
+    const int rows = nblk / blocks_per_row;
+    HIP_TRY(hipMemcpyAsync(h->d_sp_in, in, (kHistory + (size_t)nblk * kBlock) * sizeof(int16_t), hipMemcpyHostToDevice,
+                           h->stream));
+    const int rc = spectrum_launch(h, h->d_sp_in, nblk, blocks_per_row, h->d_sp_out, h->stream);
+    if (rc == SDDC_OK)
+        HIP_TRY(hipMemcpyAsync(psd, h->d_sp_out, (size_t)rows * SDDC_DDC_SPECTRUM_BINS * sizeof(float),
+                               hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // also after a failed launch: the caller's input is free again
+    return rc;
 }
 
 // ---- host path: pipelined chunks ------------------------------------------------------

@@ -45,6 +45,10 @@ extern "C" {
  * handle's controller, which learns it from the workgroups' measured start and end times
  * (fs_split_controller.hpp); 0: the built-in slot-weighted split, nothing measured. */
 #define SDDC_DDC_PARAM_FS_ADAPTIVE_SPLIT 10
+/* SDDC_DDC_PARAM_SPECTRUM_MAX_WGS = n > 0: the spectrum kernel's grid is at most n workgroups, so a
+ * workgroup takes several work items and the items outnumber the workgroups; 0 (default): full
+ * residency.  The grid changes no output bit (tests). */
+#define SDDC_DDC_PARAM_SPECTRUM_MAX_WGS 11
 
 int sddc_ddc_internal_set_param(sddc_ddc_t *h, int param, int value);
 /* A given table of n relative shares (n = the d = 0 kernel's full-residency grid, 4 x CUs) used as

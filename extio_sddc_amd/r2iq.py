@@ -76,6 +76,28 @@ def channel_tuning(offsets, d: int):
     return tbs, fcs
 
 
+FFTN = 8192                 # SDDC_DDC_FFTN: samples per frame, the spectrum window's length
+SPECTRUM_BINS = 4096        # SDDC_DDC_SPECTRUM_BINS
+WINDOW_RECT, WINDOW_HANN, WINDOW_BLACKMAN_HARRIS = 0, 1, 2
+_WINDOWS = {"rect": WINDOW_RECT, "hann": WINDOW_HANN, "blackman_harris": WINDOW_BLACKMAN_HARRIS}
+
+
+def spectrum_window(kind) -> np.ndarray:
+    """The library's periodic 8192-point window (sddc_ddc_spectrum_window): kind is WINDOW_RECT /
+    WINDOW_HANN / WINDOW_BLACKMAN_HARRIS or "rect" / "hann" / "blackman_harris"."""
+    code = _WINDOWS[kind.lower()] if isinstance(kind, str) else int(kind)
+    w = np.empty(FFTN, np.float32)
+    check(_lib.load().sddc_ddc_spectrum_window(code, w.ctypes.data))
+    return w
+
+
+def psd_to_dbfs(psd) -> np.ndarray:
+    """R2iq.spectrum's output in dB relative to a full-scale real tone (amplitude 32768 reads
+    32768^2 / 4 at its bin centre): 10 log10(4 psd / 32768^2); -inf where psd is 0."""
+    with np.errstate(divide="ignore"):
+        return 10.0 * np.log10(4.0 * np.asarray(psd, np.float64) / 32768.0 ** 2)
+
+
 def device_count() -> int:
     return _lib.load().sddc_ddc_device_count()
 
@@ -244,6 +266,40 @@ class R2iq:
         stride = d_out.stride(0) if d_out.dim() > 1 else per
         check(self._L.sddc_ddc_process_channels_device(self._h, d_in.data_ptr(), nblk, tb.ctypes.data, nch,
                                                        d_out.data_ptr(), stride, _stream_handle(stream)))
+
+    # -- wideband spectrum ---------------------------------------------------
+    def setSpectrumWindow(self, w) -> None:
+        """The spectrum's 8192-point window (see spectrum_window); None = rectangular (default)."""
+        if w is None:
+            check(self._L.sddc_ddc_set_spectrum_window(self._h, None))
+            return
+        w = np.ascontiguousarray(np.asarray(w, np.float32).reshape(-1))
+        if w.size != FFTN:
+            raise DDCError(-1, f"the spectrum window must hold {FFTN} values")
+        check(self._L.sddc_ddc_set_spectrum_window(self._h, w.ctypes.data))
+
+    def spectrum(self, buf: np.ndarray, blocks_per_row: int = 1) -> np.ndarray:
+        """Averaged power spectrum of buf = [history 4096 | nblk blocks] (int16), host path:
+        [nblk / blocks_per_row, 4096] float32, one row per blocks_per_row blocks (11 frames each).
+        Stateless: process()'s history is neither read nor changed."""
+        buf = np.ascontiguousarray(buf, np.int16).reshape(-1)
+        if buf.size < HALF_FFT + BLOCK or (buf.size - HALF_FFT) % BLOCK:
+            raise DDCError(-1, f"input length {buf.size} is not {HALF_FFT} + a multiple of {BLOCK}")
+        nblk = (buf.size - HALF_FFT) // BLOCK
+        if blocks_per_row < 1 or nblk % blocks_per_row:
+            raise DDCError(-1, f"blocks_per_row {blocks_per_row} must be >= 1 and divide nblk {nblk}")
+        psd = np.empty((nblk // blocks_per_row, SPECTRUM_BINS), np.float32)
+        check(self._L.sddc_ddc_spectrum_host(self._h, buf.ctypes.data, nblk, blocks_per_row, psd.ctypes.data))
+        return psd
+
+    def spectrum_device(self, d_in, nblk: int, d_psd, blocks_per_row: int = 1, stream=None) -> None:
+        """Stateless HBM path.  d_in: int16 device tensor [4096 + nblk*65536]; d_psd: float32 device
+        tensor [>= (nblk / blocks_per_row) * 4096].  Enqueued on `stream` like process_device."""
+        if blocks_per_row < 1 or nblk < 1 or nblk % blocks_per_row:
+            raise DDCError(-1, f"blocks_per_row {blocks_per_row} must be >= 1 and divide nblk {nblk}")
+        _check_device_buffers(d_in, nblk, d_psd, (nblk // blocks_per_row) * SPECTRUM_BINS)
+        check(self._L.sddc_ddc_spectrum_device(self._h, d_in.data_ptr(), nblk, blocks_per_row, d_psd.data_ptr(),
+                                               _stream_handle(stream)))
 
 
 def _check_device_buffers(d_in, nblk, d_out, out_floats, fmt=0):

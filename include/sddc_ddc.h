@@ -44,7 +44,9 @@ extern "C" {
 #define SDDC_DDC_ABI_VERSION 3   /* 2: + set_fine_tune, set_output_format, process_blocks, register_host;
                                     3: + CPU handles (SDDC_DDC_DEVICE_CPU), backend, set_history;
                                        still 3: + set_channel_fine_tune, channel_tuning (new symbols
-                                       only, no existing call changed) */
+                                       only, no existing call changed);
+                                       still 3: + spectrum_window, set_spectrum_window, spectrum_device,
+                                       spectrum_host (new symbols only) */
 
 #define SDDC_DDC_HALF_FFT   4096    /* halfFft               fft_mt_r2iq.h:18 */
 #define SDDC_DDC_FFTN       8192    /* FFTN_R_ADC            config.h:49 */
@@ -198,6 +200,41 @@ int sddc_ddc_process_host(sddc_ddc_t *h, const int16_t *in, int nblk, void *out)
  * Core/dsp/ringbuffer.h): block i is blocks[i] (65536 int16). */
 int sddc_ddc_process_blocks(sddc_ddc_t *h, const int16_t *const *blocks, int nblk,
                             void *out);
+
+/* ---- wideband averaged power spectrum (panadapter / waterfall) ----------------
+ * The Welch spectrum of the ADC stream on the DDC's own frame schedule.  The input is the
+ * buffer process_device takes, [history 4096 | nblk blocks of 65536] int16; frame k of block b is
+ * the 8192 samples at 65536 b + 6144 k, k = 0..10.  With the window w[0..8191] and x the sample
+ * as float (de-randomised when the handle's rand is on):
+ *   X_f[k]    = sum_j w[j] x_f[j] e^{-2 pi i jk/8192}            k = 0..4095 (bin 4096 is not output)
+ *   psd[r][k] = 1/(11 bpr) sum_{frames f of row r} |X_f[k]|^2 / (sum_j w[j])^2
+ * Row r covers blocks r bpr .. r bpr + bpr - 1 (bpr = blocks_per_row >= 1, a divisor of nblk);
+ * the output is nblk/bpr rows of SDDC_DDC_SPECTRUM_BINS float32, contiguous.  A real tone of
+ * amplitude A (int16 units) at a bin centre reads A^2/4, so dBFS = 10 log10(4 psd / 32768^2).
+ * The scale 1/(11 bpr (sum w)^2) is formed in double and applied once, at the final store.  Every
+ * sum is taken in a fixed order given by a frame's place in its row: the output is bit-identical
+ * from run to run, on any stream and for any grid.  The spectrum ignores d, the tune bin, the
+ * sideband, the output format and both NCOs; it uses the handle's rand. */
+#define SDDC_DDC_SPECTRUM_BINS 4096
+#define SDDC_DDC_WINDOW_RECT 0
+#define SDDC_DDC_WINDOW_HANN 1
+#define SDDC_DDC_WINDOW_BLACKMAN_HARRIS 2   /* 4-term, 0.35875/0.48829/0.14128/0.01168 */
+/* periodic (DFT-even) windows over 8192 points, evaluated in double, rounded once */
+int sddc_ddc_spectrum_window(int kind, float *w /* [8192] */);
+/* host array of 8192 floats copied to the handle (and device); NULL = rectangular (default).
+ * SDDC_ERR_ARG: a non-finite value or sum <= 0.  A change waits for the handle's spectrum
+ * launches in flight (the rule of set_channel_fine_tune). */
+int sddc_ddc_set_spectrum_window(sddc_ddc_t *h, const float *w);
+/* GPU handles; stateless; enqueued on hip_stream, returns after launch. d_psd 4-byte aligned.
+ * With blocks_per_row > 1 the call keeps nblk partial rows (16 KB each) in device memory of the
+ * handle, grown on demand; calls that share them are ordered one after the other, whatever
+ * their streams.  A CPU handle returns SDDC_ERR_STATE. */
+int sddc_ddc_spectrum_device(sddc_ddc_t *h, const int16_t *d_in, int nblk, int blocks_per_row,
+                             float *d_psd, void *hip_stream);
+/* Host buffers, the same [4096 + nblk*65536] layout (stateless: it neither reads nor changes the
+ * history kept by process_host).  GPU handle: copy, kernel, copy back, synchronous.  CPU handle:
+ * the AVX2 backend. */
+int sddc_ddc_spectrum_host(sddc_ddc_t *h, const int16_t *in, int nblk, int blocks_per_row, float *psd);
 
 /* ---- ingest ---------------------------------------
  * Pin a caller-owned host region (hipHostRegister) so the host path DMAs blocks
