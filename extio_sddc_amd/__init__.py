@@ -8,8 +8,9 @@ from .r2iq import (BBRF103_GAINFACTOR, BLOCK, FRAMES, HALF_FFT, NDEC, OUT_BLOCK,
                    R2iq, channel_tuning, device_count, filter_response, filter_taps, kaiser, output_samples)
 from .r2iq import (FFTN, SPECTRUM_BINS, WINDOW_BLACKMAN_HARRIS, WINDOW_HANN, WINDOW_RECT,  # noqa: F401
                    psd_to_dbfs, spectrum_window)
+from .r2iq import CHANNEL_SPECTRUM_SIZES, window  # noqa: F401
 
 __all__ = ["R2iq", "DDCError", "DEVICE_CPU", "BACKEND_CPU", "BACKEND_HIP", "build", "load", "kaiser", "filter_taps", "filter_response",
            "channel_tuning", "device_count", "output_samples", "HALF_FFT", "BLOCK", "FRAMES", "NDEC", "OUT_BLOCK",
            "BBRF103_GAINFACTOR", "spectrum_window", "psd_to_dbfs", "FFTN", "SPECTRUM_BINS", "WINDOW_RECT", "WINDOW_HANN",
-           "WINDOW_BLACKMAN_HARRIS"]
+           "WINDOW_BLACKMAN_HARRIS", "window", "CHANNEL_SPECTRUM_SIZES"]

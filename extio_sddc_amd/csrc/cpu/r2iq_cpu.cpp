@@ -274,5 +274,51 @@ void R2iq::spectrum(const int16_t *in, int nblk, int bpr, const float *w, float 
     }
 }
 
+// The channel spectrum (sddc_ddc_channel_spectrum_host on a CPU handle): per frame the windowed
+// samples through the n-point forward plan, |X|^2 added per bin in frame order (plain float
+// multiplies and adds: contraction is off), one scale and the n/2 rotation at the end.
+void R2iq::channel_spectrum(const void *iq, bool cs16, int nch, size_t stride, int n, int hop, int fpr, int nrows,
+                            const float *w, float scale, float *psd)
+{
+    Buf &B = *b_;   // n <= 4096: the frame buffers hold it
+    const FftPlan *plan = nullptr;
+    for (const auto &p : csp_)
+        if (p->size() == n) plan = p.get();
+    if (!plan) {
+        csp_.emplace_back(new FftPlan(n));
+        plan = csp_.back().get();
+    }
+    std::vector<float> acc((size_t)n);
+    for (int c = 0; c < nch; c++) {
+        for (int row = 0; row < nrows; row++) {
+            std::fill(acc.begin(), acc.end(), 0.f);
+            for (int f = 0; f < fpr; f++) {
+                const size_t start = (size_t)c * stride + ((size_t)row * (size_t)fpr + (size_t)f) * (size_t)hop;
+                float *re = B.ar.p, *im = B.ai.p;
+                if (cs16) {
+                    const int16_t *x = static_cast<const int16_t *>(iq) + 2 * start;
+                    for (int j = 0; j < n; j++) {
+                        re[j] = w ? w[j] * (float)x[2 * j] : (float)x[2 * j];
+                        im[j] = w ? w[j] * (float)x[2 * j + 1] : (float)x[2 * j + 1];
+                    }
+                } else {
+                    const float *x = static_cast<const float *>(iq) + 2 * start;
+                    for (int j = 0; j < n; j++) {
+                        re[j] = w ? w[j] * x[2 * j] : x[2 * j];
+                        im[j] = w ? w[j] * x[2 * j + 1] : x[2 * j + 1];
+                    }
+                }
+                if (plan->forward(B.ar.p, B.ai.p, B.br.p, B.bi.p)) {
+                    re = B.br.p;
+                    im = B.bi.p;
+                }
+                for (int k = 0; k < n; k++) acc[(size_t)k] += re[k] * re[k] + im[k] * im[k];
+            }
+            float *out = psd + ((size_t)c * (size_t)nrows + (size_t)row) * (size_t)n;
+            for (int q = 0; q < n; q++) out[q] = acc[(size_t)((q + n / 2) & (n - 1))] * scale;
+        }
+    }
+}
+
 }  // namespace cpu
 }  // namespace sddc

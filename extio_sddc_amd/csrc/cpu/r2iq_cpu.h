@@ -61,6 +61,12 @@ public:
     // 11 bpr frames of blocks r bpr .. r bpr + bpr - 1 in frame order; w = the 8192-point window
     // (null: rectangular).  Stateless: it neither reads nor changes the kept history.
     void spectrum(const int16_t *in, int nblk, int bpr, const float *w, float scale, bool rand, float *psd);
+    // The channel spectrum (sddc_ddc.h, sddc_ddc_channel_spectrum_host): nch streams of complex
+    // samples (cs16: int16 (I, Q), else float (I, Q)), channel c at c * stride samples; frame f of
+    // row r = the n samples at (r fpr + f) hop, windowed by w[n] (null: rectangular);
+    // psd[c][r][q] = scale x the sum over the row's frames, in frame order, of |X_f[(q + n/2) mod n]|^2.
+    void channel_spectrum(const void *iq, bool cs16, int nch, size_t stride, int n, int hop, int fpr, int nrows,
+                          const float *w, float scale, float *psd);
 
 private:
     struct Buf;
@@ -74,6 +80,7 @@ private:
     int pq_d_ = -1, pq_tb_ = -1;
     int lo_ = 0, hi_ = 0;                           // valid m ranges of the (P, Q) table
     std::vector<float> sw_;                         // spectrum(): W_8192^k, k <= 2048, as (cos, sin)
+    std::vector<std::unique_ptr<FftPlan>> csp_;     // channel_spectrum(): the plans used so far
 };
 
 }  // namespace cpu

@@ -178,6 +178,18 @@ hipError_t launch_spectrum(const KernelTables &t, const int16_t *d_in, int nblk,
 hipError_t launch_spectrum_reduce(const float *d_partial, int rows, int blocks_per_row, float scale, float *d_psd,
                                   hipStream_t s);
 
+// Channel spectrum (ddc_channel_spectrum.hip, sddc_ddc_channel_spectrum_device): the averaged
+// power spectrum of nch IQ streams in the DDC's output format (cs16: int16 (I, Q) pairs, else
+// float pairs), channel c at d_iq + c * stride_samples complex samples.  One work item per
+// (channel, row): its fpr frames of n samples (n = 256..4096, frame f of row r at sample
+// (r fpr + f) hop) are transformed and |X|^2 summed in frame order by the n / 16 threads that own
+// it; d_psd[c][r][q] = scale x the sum at bin (q + n/2) mod n, 4-byte aligned.  d_window: n
+// floats, or nullptr for the rectangular window (no multiply).  max_wgs > 0 caps the grid (tests).
+// The caller has checked that every frame lies inside its stream.
+hipError_t launch_channel_spectrum(const KernelTables &t, const void *d_iq, int cs16, int nch, int nrows,
+                                   size_t stride_samples, int n, int hop, int fpr, float *d_psd,
+                                   const float *d_window, float scale, int max_wgs, int device, hipStream_t s);
+
 // batched FFTs (fft_batch.hip, include/sddc_fft.h); fft_prepare fills the device's twiddle
 // table once (synchronises s the first time)
 hipError_t fft_prepare(hipStream_t s);

@@ -286,6 +286,20 @@ struct sddc_ddc {
     Readers sp_readers;
     int sp_max_wgs = 0;                    // SDDC_DDC_PARAM_SPECTRUM_MAX_WGS
 
+    // channel spectrum (sddc_ddc_channel_spectrum_*): the window with its length (chsp_n == 0:
+    // rectangular) and its sum, its device copy, and the host call's device buffers (grown on
+    // demand).  The launches keep no other state; chsp_readers holds their streams, and a change of
+    // the window waits for all of them.
+    std::vector<float> chsp_win;
+    int chsp_n = 0;
+    double chsp_wsum = 0.0;
+    float *d_chsp_win = nullptr;           // [4096]
+    void *d_chsp_in = nullptr;             // channel_spectrum_host
+    float *d_chsp_out = nullptr;
+    size_t chsp_in_cap = 0, chsp_out_cap = 0;   // bytes, floats
+    Readers chsp_readers;
+    int chsp_max_wgs = 0;                  // SDDC_DDC_PARAM_CHSPEC_MAX_WGS
+
     // CPU handle (device SDDC_DDC_DEVICE_CPU): the AVX2 backend; no HIP object above exists
     std::unique_ptr<sddc::cpu::R2iq> cpu;
 
@@ -500,6 +514,7 @@ int sddc_ddc_destroy(sddc_ddc_t *h)
         (void)h->readers.sync();
         (void)h->ch_readers.sync();
         (void)h->sp_readers.sync();
+        (void)h->chsp_readers.sync();
         if (h->d_tables) (void)hipFree(h->d_tables);
         for (auto &sl : h->hs) {
             if (sl.d_in) (void)hipFree(sl.d_in);
@@ -527,6 +542,10 @@ int sddc_ddc_destroy(sddc_ddc_t *h)
         if (h->d_sp_in) (void)hipFree(h->d_sp_in);
         if (h->d_sp_out) (void)hipFree(h->d_sp_out);
         h->sp_readers.clear();
+        if (h->d_chsp_win) (void)hipFree(h->d_chsp_win);
+        if (h->d_chsp_in) (void)hipFree(h->d_chsp_in);
+        if (h->d_chsp_out) (void)hipFree(h->d_chsp_out);
+        h->chsp_readers.clear();
         if (h->fsa.h_ring) (void)hipHostFree(h->fsa.h_ring);   // its writers were waited for above
         h->readers.clear();
         h->ch_readers.clear();
@@ -1037,6 +1056,10 @@ int sddc_ddc_internal_set_param(sddc_ddc_t *h, int param, int value)
         if (value < 0) return fail(SDDC_ERR_ARG, "spectrum workgroup cap %d is negative", value);
         h->sp_max_wgs = value;
         return SDDC_OK;
+    case SDDC_DDC_PARAM_CHSPEC_MAX_WGS:
+        if (value < 0) return fail(SDDC_ERR_ARG, "channel spectrum workgroup cap %d is negative", value);
+        h->chsp_max_wgs = value;
+        return SDDC_OK;
     default:
         return fail(SDDC_ERR_ARG, "unknown parameter %d", param);
     }
@@ -1274,10 +1297,10 @@ int sddc_ddc_process_channels_device(sddc_ddc_t *h, const int16_t *d_in, int nbl
 }
 
 /* ---- wideband averaged power spectrum --------------------------------------------------- */
-int sddc_ddc_spectrum_window(int kind, float *w)
+// periodic (DFT-even) cosine-sum windows over n points, evaluated in double and rounded once
+static int cosine_window(const char *who, int kind, int n, float *w)
 {
-    if (!w) return fail(SDDC_ERR_ARG, "spectrum_window: null array");
-    // periodic (DFT-even) cosine-sum windows, evaluated in double and rounded once
+    if (!w) return fail(SDDC_ERR_ARG, "%s: null array", who);
     static const double kRect[] = {1.0}, kHann[] = {0.5, 0.5}, kBh[] = {0.35875, 0.48829, 0.14128, 0.01168};
     const double *a;
     int na;
@@ -1285,14 +1308,23 @@ int sddc_ddc_spectrum_window(int kind, float *w)
     case SDDC_DDC_WINDOW_RECT: a = kRect, na = 1; break;
     case SDDC_DDC_WINDOW_HANN: a = kHann, na = 2; break;
     case SDDC_DDC_WINDOW_BLACKMAN_HARRIS: a = kBh, na = 4; break;
-    default: return fail(SDDC_ERR_ARG, "spectrum_window: unknown window %d", kind);
+    default: return fail(SDDC_ERR_ARG, "%s: unknown window %d", who, kind);
     }
-    for (int j = 0; j < SDDC_DDC_FFTN; j++) {
+    for (int j = 0; j < n; j++) {
         double v = 0.0;
-        for (int m = 0; m < na; m++) v += ((m & 1) ? -a[m] : a[m]) * std::cos(2.0 * M_PI * m * j / SDDC_DDC_FFTN);
+        for (int m = 0; m < na; m++) v += ((m & 1) ? -a[m] : a[m]) * std::cos(2.0 * M_PI * m * j / n);
         w[j] = (float)v;
     }
     return SDDC_OK;
+}
+
+int sddc_ddc_spectrum_window(int kind, float *w) { return cosine_window("spectrum_window", kind, SDDC_DDC_FFTN, w); }
+
+int sddc_ddc_window(int kind, int n, float *w)
+{
+    if (n < 32 || n > 8192 || (n & (n - 1)) != 0)
+        return fail(SDDC_ERR_ARG, "window: n must be a power of two in 32..8192 (got %d)", n);
+    return cosine_window("window", kind, n, w);
 }
 
 int sddc_ddc_set_spectrum_window(sddc_ddc_t *h, const float *w)
@@ -1422,6 +1454,149 @@ int sddc_ddc_spectrum_host(sddc_ddc_t *h, const int16_t *in, int nblk, int block
     if (rc == SDDC_OK)
         HIP_TRY(hipMemcpyAsync(psd, h->d_sp_out, (size_t)rows * SDDC_DDC_SPECTRUM_BINS * sizeof(float),
                                hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // also after a failed launch: the caller's input is free again
+    return rc;
+}
+
+/* ---- channel spectrum: the averaged power spectrum of the DDC's IQ output ----------------- */
+static bool chsp_size(int n) { return n == 256 || n == 512 || n == 1024 || n == 2048 || n == 4096; }
+
+int sddc_ddc_set_channel_spectrum_window(sddc_ddc_t *h, const float *w, int n)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    double sum = 0.0;
+    if (w) {
+        if (!chsp_size(n)) return fail(SDDC_ERR_ARG, "channel spectrum window: n must be 256, 512, 1024, 2048 or 4096 (got %d)", n);
+        for (int j = 0; j < n; j++) {
+            if (!std::isfinite(w[j])) return fail(SDDC_ERR_ARG, "channel spectrum window: value %d is not finite", j);
+            sum += w[j];
+        }
+        if (!(sum > 0.0)) return fail(SDDC_ERR_ARG, "channel spectrum window: the sum of the window must be > 0");
+    }
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (w && !h->cpu) {
+        DeviceGuard g(h->device);
+        HIP_TRY(g.err);
+        HIP_TRY(h->chsp_readers.sync());   // earlier launches, on any stream, may still read the device copy
+        if (!h->d_chsp_win) HIP_TRY(hipMalloc(&h->d_chsp_win, 4096 * sizeof(float)));
+        h->chsp_win.clear();               // a failed upload leaves the rectangular window
+        h->chsp_n = 0;
+        HIP_TRY(hipMemcpy(h->d_chsp_win, w, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    }
+    if (w) h->chsp_win.assign(w, w + n);
+    else h->chsp_win.clear();
+    h->chsp_n = w ? n : 0;
+    h->chsp_wsum = sum;
+    return SDDC_OK;
+}
+
+// the checks both calls share (under h->mu: the format and the window are read here)
+static int check_chsp_args(const sddc_ddc_t *h, const void *iq, int nch, size_t nsamp, size_t in_stride, int n,
+                           int hop, int fpr, int nrows, const float *psd)
+{
+    if (!chsp_size(n)) return fail(SDDC_ERR_ARG, "channel spectrum: n must be 256, 512, 1024, 2048 or 4096 (got %d)", n);
+    if (nch < 1 || nch > SDDC_DDC_MAX_CHANNELS)
+        return fail(SDDC_ERR_ARG, "nch must be in 1..%d (got %d)", SDDC_DDC_MAX_CHANNELS, nch);
+    if (hop < 1 || fpr < 1 || nrows < 1)
+        return fail(SDDC_ERR_ARG, "hop, frames_per_row and nrows must be >= 1 (got %d, %d, %d)", hop, fpr, nrows);
+    if ((unsigned long long)nch * (unsigned long long)nrows > 0x7fffffffULL || nsamp > ((size_t)1 << 48))
+        return fail(SDDC_ERR_ARG, "nch * nrows must be below 2^31 and nsamp at most 2^48");
+    // (nrows fpr - 1) hop + n <= nsamp, without overflow
+    const unsigned long long frames = (unsigned long long)nrows * (unsigned long long)fpr;
+    if (nsamp < (size_t)n || (frames - 1) > (unsigned long long)(nsamp - (size_t)n) / (unsigned long long)hop)
+        return fail(SDDC_ERR_ARG, "%d rows of %d frames at hop %d need more than the %zu samples given", nrows, fpr,
+                    hop, nsamp);
+    if (nch > 1 && (in_stride < 2 * nsamp || (in_stride & 1) != 0))
+        return fail(SDDC_ERR_ARG, "in_stride must be even and >= 2 nsamp (got %zu, nsamp %zu)", in_stride, nsamp);
+    if (!iq || !psd) return fail(SDDC_ERR_ARG, "null buffer");
+    const uintptr_t sample = h->out_fmt == SDDC_DDC_FMT_CS16 ? 4 : 8;
+    if (((uintptr_t)iq & (sample - 1)) != 0) return fail(SDDC_ERR_ARG, "iq must be %d-byte aligned", (int)sample);
+    if (((uintptr_t)psd & 3) != 0) return fail(SDDC_ERR_ARG, "psd must be 4-byte aligned");
+    if (h->chsp_n != 0 && h->chsp_n != n)
+        return fail(SDDC_ERR_STATE, "the channel spectrum window has %d points, the call asks for n = %d", h->chsp_n, n);
+    return SDDC_OK;
+}
+
+// 1 / (fpr (sum w)^2 s^2) in double; s = cs16_scale under CS16 (the samples enter as integers)
+static double chsp_scale(const sddc_ddc_t *h, int n, int fpr)
+{
+    const double wsum = h->chsp_n ? h->chsp_wsum : (double)n;
+    const double s = h->out_fmt == SDDC_DDC_FMT_CS16 ? (double)h->cs16_scale : 1.0;
+    return 1.0 / ((double)fpr * wsum * wsum * s * s);
+}
+
+static int chsp_launch(sddc_ddc_t *h, const void *d_iq, int nch, size_t in_stride, int n, int hop, int fpr, int nrows,
+                       float *d_psd, hipStream_t s)
+{
+    const hipError_t e = sddc::launch_channel_spectrum(h->tables, d_iq, h->out_fmt == SDDC_DDC_FMT_CS16, nch, nrows,
+                                                       in_stride / 2, n, hop, fpr, d_psd,
+                                                       h->chsp_n ? h->d_chsp_win : nullptr, (float)chsp_scale(h, n, fpr),
+                                                       h->chsp_max_wgs, h->device, s);
+    const hipError_t er = h->chsp_readers.record(s);   // whatever was enqueued stays ordered before a window change
+    HIP_TRY(e);
+    HIP_TRY(er);
+    return SDDC_OK;
+}
+
+int sddc_ddc_channel_spectrum_device(sddc_ddc_t *h, const void *d_iq, int nch, size_t nsamp, size_t in_stride, int n,
+                                     int hop, int frames_per_row, int nrows, float *d_psd, void *hip_stream)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(h->mu);   // the call reads the format and the window: one consistent set
+    if (h->cpu) return fail(SDDC_ERR_STATE, "channel_spectrum_device: a CPU handle has no device path");
+    if (int rc = check_chsp_args(h, d_iq, nch, nsamp, in_stride, n, hop, frames_per_row, nrows, d_psd)) return rc;
+    DeviceGuard g(h->device);
+    HIP_TRY(g.err);
+    return chsp_launch(h, d_iq, nch, in_stride, n, hop, frames_per_row, nrows, d_psd, (hipStream_t)hip_stream);
+}
+
+int sddc_ddc_channel_spectrum_host(sddc_ddc_t *h, const void *iq, int nch, size_t nsamp, size_t in_stride, int n,
+                                   int hop, int frames_per_row, int nrows, float *psd)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (int rc = check_chsp_args(h, iq, nch, nsamp, in_stride, n, hop, frames_per_row, nrows, psd)) return rc;
+    const bool cs16 = h->out_fmt == SDDC_DDC_FMT_CS16;
+    if (h->cpu) {
+        try {
+            h->cpu->channel_spectrum(iq, cs16, nch, nch > 1 ? in_stride / 2 : 0, n, hop, frames_per_row, nrows,
+                                     h->chsp_n ? h->chsp_win.data() : nullptr,
+                                     (float)chsp_scale(h, n, frames_per_row), psd);
+        } catch (const std::exception &ex) {
+            return fail(SDDC_ERR_NOMEM, "cpu backend: %s", ex.what());
+        }
+        return SDDC_OK;
+    }
+    DeviceGuard g(h->device);
+    HIP_TRY(g.err);
+    // the span that holds every channel's nsamp samples, and the rows
+    const size_t in_bytes = ((size_t)(nch - 1) * (nch > 1 ? in_stride : 0) + 2 * nsamp) * (cs16 ? 2 : 4);
+    const size_t out_floats = (size_t)nch * (size_t)nrows * (size_t)n;
+    // the earlier host calls were synchronous: nothing reads the old buffers
+    if (in_bytes > h->chsp_in_cap) {
+        if (h->d_chsp_in) (void)hipFree(h->d_chsp_in);
+        h->d_chsp_in = nullptr;
+        h->chsp_in_cap = 0;
+        if (hipMalloc(&h->d_chsp_in, in_bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(SDDC_ERR_NOMEM, "channel_spectrum_host: no device memory for %zu input bytes", in_bytes);
+        }
+        h->chsp_in_cap = in_bytes;
+    }
+    if (out_floats > h->chsp_out_cap) {
+        if (h->d_chsp_out) (void)hipFree(h->d_chsp_out);
+        h->d_chsp_out = nullptr;
+        h->chsp_out_cap = 0;
+        if (hipMalloc(&h->d_chsp_out, out_floats * sizeof(float)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(SDDC_ERR_NOMEM, "channel_spectrum_host: no device memory for %zu output floats", out_floats);
+        }
+        h->chsp_out_cap = out_floats;
+    }
+    HIP_TRY(hipMemcpyAsync(h->d_chsp_in, iq, in_bytes, hipMemcpyHostToDevice, h->stream));
+    const int rc = chsp_launch(h, h->d_chsp_in, nch, in_stride, n, hop, frames_per_row, nrows, h->d_chsp_out, h->stream);
+    if (rc == SDDC_OK)
+        HIP_TRY(hipMemcpyAsync(psd, h->d_chsp_out, out_floats * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));   // also after a failed launch: the caller's input is free again
     return rc;
 }

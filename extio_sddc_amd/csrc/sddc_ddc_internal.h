@@ -49,6 +49,11 @@ extern "C" {
  * workgroup takes several work items and the items outnumber the workgroups; 0 (default): full
  * residency.  The grid changes no output bit (tests). */
 #define SDDC_DDC_PARAM_SPECTRUM_MAX_WGS 11
+/* SDDC_DDC_PARAM_CHSPEC_MAX_WGS = n > 0: the channel spectrum kernel's grid is at most n workgroups,
+ * so a workgroup takes several rounds of work items and the last round is partial; 0 (default):
+ * enough workgroups for all items, or full residency with a loop.  The grid changes no output bit
+ * (tests). */
+#define SDDC_DDC_PARAM_CHSPEC_MAX_WGS 12
 
 int sddc_ddc_internal_set_param(sddc_ddc_t *h, int param, int value);
 /* A given table of n relative shares (n = the d = 0 kernel's full-residency grid, 4 x CUs) used as

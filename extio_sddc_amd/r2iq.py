@@ -91,6 +91,18 @@ def spectrum_window(kind) -> np.ndarray:
     return w
 
 
+CHANNEL_SPECTRUM_SIZES = (256, 512, 1024, 2048, 4096)
+
+
+def window(kind, n: int) -> np.ndarray:
+    """The library's periodic n-point window (sddc_ddc_window; n = 2^k, 32..8192): kind as for
+    spectrum_window.  window(kind, 8192) equals spectrum_window(kind) bit for bit."""
+    code = _WINDOWS[kind.lower()] if isinstance(kind, str) else int(kind)
+    w = np.empty(max(int(n), 0), np.float32)
+    check(_lib.load().sddc_ddc_window(code, int(n), w.ctypes.data))
+    return w
+
+
 def psd_to_dbfs(psd) -> np.ndarray:
     """R2iq.spectrum's output in dB relative to a full-scale real tone (amplitude 32768 reads
     32768^2 / 4 at its bin centre): 10 log10(4 psd / 32768^2); -inf where psd is 0."""
@@ -300,6 +312,70 @@ class R2iq:
         _check_device_buffers(d_in, nblk, d_psd, (nblk // blocks_per_row) * SPECTRUM_BINS)
         check(self._L.sddc_ddc_spectrum_device(self._h, d_in.data_ptr(), nblk, blocks_per_row, d_psd.data_ptr(),
                                                _stream_handle(stream)))
+
+
+    # -- channel spectrum ------------------------------------------------------
+    def setChannelSpectrumWindow(self, w) -> None:
+        """The channel spectrum's window (see window); its length, one of CHANNEL_SPECTRUM_SIZES, is
+        the n of the calls that follow.  None = rectangular (default), for any n."""
+        if w is None:
+            check(self._L.sddc_ddc_set_channel_spectrum_window(self._h, None, 0))
+            return
+        w = np.ascontiguousarray(np.asarray(w, np.float32).reshape(-1))
+        check(self._L.sddc_ddc_set_channel_spectrum_window(self._h, w.ctypes.data, w.size))
+
+    def channel_spectrum(self, iq: np.ndarray, n: int, hop: int = None, frames_per_row: int = 1,
+                         nrows: int = None) -> np.ndarray:
+        """Averaged power spectrum of the DDC's IQ output, host path: iq is complex64 [nch, nsamp]
+        (CF32) or int16 [nch, nsamp, 2] (CS16), matching the handle's output format; a single
+        stream may drop the channel axis.  Frame f of row r is the n samples at
+        (r * frames_per_row + f) * hop (hop defaults to n / 2), nrows defaults to all whole rows.
+        Returns float32 [nch, nrows, n], q = n / 2 the channel's centre, ascending in frequency."""
+        iq = np.asarray(iq)
+        if self._fmt == FMT_CS16:
+            if iq.dtype != np.int16 or iq.ndim not in (2, 3) or iq.shape[-1] != 2:
+                raise DDCError(-1, "CS16 handle: iq must be int16 [nch, nsamp, 2]")
+            iq = np.ascontiguousarray(iq.reshape((1,) + iq.shape if iq.ndim == 2 else iq.shape))
+        else:
+            if iq.dtype != np.complex64 or iq.ndim not in (1, 2):
+                raise DDCError(-1, "CF32 handle: iq must be complex64 [nch, nsamp]")
+            iq = np.ascontiguousarray(iq.reshape(1, -1) if iq.ndim == 1 else iq)
+        nch, nsamp = iq.shape[0], iq.shape[1]
+        hop = n // 2 if hop is None else int(hop)
+        if hop < 1 or frames_per_row < 1 or nsamp < n:
+            raise DDCError(-1, f"hop {hop}, frames_per_row {frames_per_row} must be >= 1 and nsamp {nsamp} >= n {n}")
+        if nrows is None:
+            nrows = ((nsamp - n) // hop + 1) // frames_per_row
+        if nrows < 1:
+            raise DDCError(-1, f"{nsamp} samples do not hold one row of {frames_per_row} frames")
+        psd = np.empty((nch, nrows, max(int(n), 0)), np.float32)
+        check(self._L.sddc_ddc_channel_spectrum_host(self._h, iq.ctypes.data, nch, nsamp, 2 * nsamp, int(n), hop,
+                                                     int(frames_per_row), int(nrows), psd.ctypes.data))
+        return psd
+
+    def channel_spectrum_device(self, d_iq, nch: int, nsamp: int, in_stride: int, n: int, hop: int,
+                                frames_per_row: int, nrows: int, d_psd, stream=None) -> None:
+        """Stateless HBM path on the buffer process_device / process_channels_device wrote: d_iq is a
+        float32 (CS16: int16) device tensor, channel c at c * in_stride components, nsamp complex
+        samples each; d_psd float32 [>= nch * nrows * n].  Enqueued on `stream` like process_device."""
+        import torch
+        if not (d_iq.is_cuda and d_psd.is_cuda):
+            raise DDCError(-1, "device path needs device tensors")
+        want = torch.int16 if self._fmt == FMT_CS16 else torch.float32
+        if d_iq.dtype != want or d_psd.dtype != torch.float32:
+            raise DDCError(-1, f"d_iq must be {want} and d_psd float32")
+        if not (d_iq.is_contiguous() and d_psd.is_contiguous()):
+            raise DDCError(-1, "tensors must be contiguous")
+        if nch < 1 or nsamp < 1 or nrows < 1 or n < 1:
+            raise DDCError(-1, "nch, nsamp, nrows and n must be >= 1")
+        need = (nch - 1) * in_stride + 2 * nsamp
+        if d_iq.numel() < need:
+            raise DDCError(-1, f"d_iq has {d_iq.numel()} components, need {need}")
+        if d_psd.numel() < nch * nrows * n:
+            raise DDCError(-1, f"d_psd has {d_psd.numel()} floats, need {nch * nrows * n}")
+        check(self._L.sddc_ddc_channel_spectrum_device(self._h, d_iq.data_ptr(), nch, nsamp, in_stride, n, hop,
+                                                       frames_per_row, nrows, d_psd.data_ptr(),
+                                                       _stream_handle(stream)))
 
 
 def _check_device_buffers(d_in, nblk, d_out, out_floats, fmt=0):

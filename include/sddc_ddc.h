@@ -46,7 +46,9 @@ extern "C" {
                                        still 3: + set_channel_fine_tune, channel_tuning (new symbols
                                        only, no existing call changed);
                                        still 3: + spectrum_window, set_spectrum_window, spectrum_device,
-                                       spectrum_host (new symbols only) */
+                                       spectrum_host (new symbols only);
+                                       still 3: + window, set_channel_spectrum_window,
+                                       channel_spectrum_device, channel_spectrum_host (new symbols only) */
 
 #define SDDC_DDC_HALF_FFT   4096    /* halfFft               fft_mt_r2iq.h:18 */
 #define SDDC_DDC_FFTN       8192    /* FFTN_R_ADC            config.h:49 */
@@ -235,6 +237,54 @@ int sddc_ddc_spectrum_device(sddc_ddc_t *h, const int16_t *d_in, int nblk, int b
  * history kept by process_host).  GPU handle: copy, kernel, copy back, synchronous.  CPU handle:
  * the AVX2 backend. */
 int sddc_ddc_spectrum_host(sddc_ddc_t *h, const int16_t *in, int nblk, int blocks_per_row, float *psd);
+
+/* ---- channel spectrum: the averaged power spectrum of the DDC's IQ output -----------------
+ * The "zoom" panadapter / waterfall of a tuned channel, on the decimated stream, so its resolution
+ * scales with the decimation (n = 4096 at d = 6 resolves fs / 2^19 per bin).  The input is what
+ * process_device or process_channels_device wrote: nch channel streams, channel c starting
+ * c*in_stride components into the buffer (a component is a float for CF32 and an int16 for CS16,
+ * two per complex sample), nsamp complex samples each.  The call reads the buffer in the handle's
+ * CURRENT output format (sddc_ddc_set_output_format); under CS16 the sample value is
+ * v / cs16_scale.  With the window w[0..n-1] and fpr = frames_per_row, frame f of row r starts at
+ * sample (r*fpr + f)*hop:
+ *   X_f[k]       = sum_j w[j] x[start_f + j] e^{-2 pi i jk/n}                              k = 0..n-1
+ *   psd[c][r][q] = 1/fpr sum_{f < fpr} |X_f[(q + n/2) mod n]|^2 / (sum_j w[j])^2          q = 0..n-1
+ * Output index q ascends in frequency: q = n/2 is the channel's centre (DC), q = 0 is -fs_out/2.
+ * The output is [nch][nrows][n] float32, contiguous.  A complex tone of amplitude A at a bin centre
+ * reads A^2.  n is 256, 512, 1024, 2048 or 4096; hop >= 1 is any integer and may exceed n;
+ * fpr >= 1, nrows >= 1, 1 <= nch <= SDDC_DDC_MAX_CHANNELS.  The call needs
+ * (nrows*fpr - 1)*hop + n <= nsamp and, when nch > 1, an even in_stride >= 2*nsamp (every channel
+ * starts on a complex sample), and nch*nrows < 2^31; a violation returns SDDC_ERR_ARG.
+ * The scale 1/(fpr (sum w)^2 s^2), s = cs16_scale under CS16 and 1 under CF32, is formed in double
+ * and applied once, at the final store, so CS16 samples enter the transform as exact integers.
+ * A stored value depends only on the samples of its row and the call's parameters, through a fixed
+ * sequence of float operations (no atomics): it is bit-identical from run to run, on any stream,
+ * for any grid, for a channel computed alone or among others, and for row r of a call against
+ * row 0 of a call whose buffer starts at sample r*fpr*hop.
+ * The spectrum ignores d, the tune bin, the sideband, rand and the NCOs: it is the spectrum of the
+ * samples it is given.  With the sideband set to lsb the DDC has already conjugated them, so the
+ * display is mirrored, as the listener expects. */
+/* The three SDDC_DDC_WINDOW_* kinds over n points (n = 2^k, 32..8192): periodic, evaluated in
+ * double, rounded once.  sddc_ddc_window(kind, 8192, w) equals sddc_ddc_spectrum_window(kind, w)
+ * bit for bit. */
+int sddc_ddc_window(int kind, int n, float *w /* [n] */);
+/* host array of n floats copied to the handle (and device); the handle keeps this one window with
+ * its length.  NULL = rectangular (default; n is then ignored and calls of any n are valid).
+ * SDDC_ERR_ARG: a non-finite value, a sum <= 0, an n outside the five sizes.  A change waits for
+ * the handle's channel-spectrum launches in flight (the rule of set_spectrum_window). */
+int sddc_ddc_set_channel_spectrum_window(sddc_ddc_t *h, const float *w, int n);
+/* GPU handles; stateless; enqueued on hip_stream, returns after launch.  d_iq aligned to one
+ * complex sample of the format (8 bytes CF32, 4 bytes CS16), d_psd 4-byte aligned.  Another n
+ * than the stored window's returns SDDC_ERR_STATE, as does a CPU handle.  One work item per
+ * (channel, row) runs on n/16 threads, so a call with a single row of a single channel uses one
+ * sub-group of one workgroup: give it rows or channels to fill the device. */
+int sddc_ddc_channel_spectrum_device(sddc_ddc_t *h, const void *d_iq, int nch, size_t nsamp, size_t in_stride,
+                                     int n, int hop, int frames_per_row, int nrows, float *d_psd, void *hip_stream);
+/* Host buffers, the same layout.  GPU handle: copy in, kernel, copy back, synchronous, in device
+ * buffers of its own (it never touches the host path's slots or history).  CPU handle: the AVX2
+ * backend's FFT of n points, the same definition with the same single final scale. */
+int sddc_ddc_channel_spectrum_host(sddc_ddc_t *h, const void *iq, int nch, size_t nsamp, size_t in_stride,
+                                   int n, int hop, int frames_per_row, int nrows, float *psd);
 
 /* ---- ingest ---------------------------------------
  * Pin a caller-owned host region (hipHostRegister) so the host path DMAs blocks
