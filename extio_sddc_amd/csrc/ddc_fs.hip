@@ -44,6 +44,7 @@
 #include "ddc_queue.hpp"
 #include "ddc_stamps.hpp"
 #include "ddc_fs_perm.h"
+#include "split_coeffs.h"
 
 namespace sddc {
 namespace {
@@ -592,12 +593,13 @@ __global__ __launch_bounds__(NT, 4) void r2iq_fs_kernel(
 // at b = 2048 (column 0, register 8), whose entry holds (Q, 0) instead (the kernel's wave-0 path).
 // Versus the (P, Q) float4 of round 5: 6 or 7 VALU per bin instead of 8, and 8 bytes per bin read
 // from L2 every frame instead of 16 (r is read once per launch).  tools/fs_model.py (split "pr")
-// models it.
+// models it.  P and r come from split_pr_coeffs (split_coeffs.h): W in double, never the float
+// post8192 table, whose rounding the ratio r amplifies by 1 / |b - 2048| (1e-5 at bins 2045..2051;
+// tests/test_gpu_fs4_tones.py, tests/test_split_pr_model.py).
 // fsl = [g_t | g_t W^{-t} | g_t W^{-4t}], g_t = e^{-2 pi i tb t / 4096}, looked up exactly in the
 // 4096-point table.
-__global__ void build_fs_tables_kernel(const float2 *__restrict__ hsel0, const float2 *__restrict__ post8192,
-                                       const float2 *__restrict__ tw4096, int tunebin, float4 *__restrict__ pqf,
-                                       float2 *__restrict__ fsl)
+__global__ void build_fs_tables_kernel(const float2 *__restrict__ hsel0, const float2 *__restrict__ tw4096,
+                                       int tunebin, float4 *__restrict__ pqf, float2 *__restrict__ fsl)
 {
     const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (i >= HALF) return;
@@ -607,18 +609,8 @@ __global__ void build_fs_tables_kernel(const float2 *__restrict__ hsel0, const f
     float3 c = make_float3(0.f, 0.f, 0.f);
     if (band) {
         const int m = (b - tunebin) & (HALF - 1);
-        const double hr = hsel0[m].x, hi = hsel0[m].y;
-        const double wr = post8192[b].x, wi = post8192[b].y;
-        const double pr = 1.0 + wi, pi = -wr, qr = 1.0 - wi, qi = wr;   // 1 - i W, 1 + i W
-        if (b == HALF / 2) {   // P = 0: (Q, 0)
-            c.x = (float)(hr * qr - hi * qi);
-            c.y = (float)(hr * qi + hi * qr);
-        } else {
-            c.x = (float)(hr * pr - hi * pi);
-            c.y = (float)(hr * pi + hi * pr);
-            // r = Re[(1 + i W) / (i (1 - i W))] = Re[(qr + i qi) / (-pi + i pr)]
-            c.z = (float)((-qr * pi + qi * pr) / (pi * pi + pr * pr));
-        }
+        const SplitCoeffs k = split_pr_coeffs(hsel0[m].x, hsel0[m].y, b, kSplitQ0);   // b = 2048: (Q, 0)
+        c = make_float3(k.px, k.py, k.r);
     }
     // P of rows kk and 15 - kk side by side: float2 index 2 (256 p + l) + [kk >= 8], p = min(kk, 15 - kk)
     reinterpret_cast<float2 *>(pqf)[2 * (NT * (kk < 8 ? kk : 15 - kk) + l) + (kk >= 8)] = make_float2(c.x, c.y);
@@ -746,8 +738,8 @@ bool fs_path(int d, int tunebin) { return d == 0 && (tunebin & 3) == 0; }
 hipError_t launch_build_fs_tables(const KernelTables &t, int tunebin, float4 *pqf, float2 *fsl, hipStream_t s)
 {
     if (tunebin < 0 || tunebin >= HALF || (tunebin & 3)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(build_fs_tables_kernel, dim3(HALF / 256), dim3(256), 0, s, t.hsel[0], t.post8192, t.tw4096,
-                       tunebin, pqf, fsl);
+    hipLaunchKernelGGL(build_fs_tables_kernel, dim3(HALF / 256), dim3(256), 0, s, t.hsel[0], t.tw4096, tunebin, pqf,
+                       fsl);
     return hipGetLastError();
 }
 

@@ -24,6 +24,7 @@
 #include "ddc_frame_common.hpp"
 #include "ddc_queue.hpp"
 #include "ddc_stamps.hpp"
+#include "split_coeffs.h"
 
 namespace sddc {
 namespace {
@@ -678,9 +679,11 @@ __global__ __launch_bounds__(NT, 4) void r2iq_persistent_kernel(
 // r = Q / (i P) as float from float index 2 N (split_pr), at pq_p_index / pq_r_index.  r is infinite at bin 2048 (P = 0,
 // X Hh = Q conj Zc): there r = 2^64 and P = Q / (i 2^64), exact power-of-two scalings, so that
 // P (Zk + i r conj Zc) = Q conj Zc - i 2^-64 Q Zk, the second term far below float32's resolution
-// of the first (|Zc| < 2^28: no overflow).  Evaluated in double from the float tables and rounded once.
-__global__ void build_split_filter_kernel(const float2 *__restrict__ hsel, const float2 *__restrict__ post8192,
-                                          int N, int tunebin, float4 *__restrict__ pq)
+// of the first (|Zc| < 2^28: no overflow).  Evaluated in double by split_pr_coeffs (split_coeffs.h)
+// from the float filter and a double W, rounded once: W from the float post8192 table made r
+// complex and its kept real part wrong by 1e-5 at bins 2045..2051 (tests/test_gpu_fs4_tones.py).
+__global__ void build_split_filter_kernel(const float2 *__restrict__ hsel, int N, int tunebin,
+                                          float4 *__restrict__ pq)
 {
     const int m = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (m >= N) return;
@@ -688,19 +691,9 @@ __global__ void build_split_filter_kernel(const float2 *__restrict__ hsel, const
     float2 p = make_float2(0.f, 0.f);
     float r = 0.f;
     if (bin >= 0 && bin < HALF) {
-        const double hr = hsel[m].x, hi = hsel[m].y;
-        const double wr = post8192[bin].x, wi = post8192[bin].y;
-        // 1 - i W = (1 + wi, -wr), 1 + i W = (1 - wi, wr)
-        const double pr = 1.0 + wi, pi = -wr, qr = 1.0 - wi, qi = wr;
-        if (bin == HALF / 2) {
-            constexpr double s = 0x1p-64;
-            const double q0 = hr * qr - hi * qi, q1 = hr * qi + hi * qr;
-            p = make_float2((float)(q1 * s), (float)(-q0 * s));   // -i Q 2^-64
-            r = 0x1p64f;
-        } else {
-            p = make_float2((float)(hr * pr - hi * pi), (float)(hr * pi + hi * pr));
-            r = (float)((-qr * pi + qi * pr) / (pi * pi + pr * pr));   // Re[(qr + i qi) / (-pi + i pr)]
-        }
+        const SplitCoeffs k = split_pr_coeffs(hsel[m].x, hsel[m].y, bin, kSplit2p64);
+        p = make_float2(k.px, k.py);
+        r = k.r;
     }
     reinterpret_cast<float2 *>(pq)[pq_p_index(N, m)] = p;
     reinterpret_cast<float *>(pq)[2 * N + pq_r_index(N, m)] = r;
@@ -755,8 +748,8 @@ hipError_t launch_build_split_filter(const KernelTables &t, int d, int tunebin, 
 {
     if (d < 0 || d > 6) return hipErrorInvalidValue;
     const int N = HALF >> d;
-    hipLaunchKernelGGL(build_split_filter_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, t.hsel[d],
-                       t.post8192, N, tunebin, pq);
+    hipLaunchKernelGGL(build_split_filter_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, t.hsel[d], N,
+                       tunebin, pq);
     return hipGetLastError();
 }
 

@@ -10,8 +10,9 @@
 //      (k = 0 gives bins 0 and 4096, the Nyquist bin, which is not output; bin 2048 is its own
 //      mirror, X[2048] = conj Z[2048]), accumulated in registers.
 // The (P, r) form of the DDC's split is not used: its r = cot(pi/4 - pi k / 8192) grows without
-// bound towards bin 2048, which costs precision there with the float post8192 table,
-// and there is no filter to fold into P here.
+// bound towards bin 2048 and amplifies every error of its table by as much, so the DDC builds it
+// from W in double (split_coeffs.h), not from the float post8192 table read here; the plain split
+// below does not amplify that table's rounding, and there is no filter to fold into P here.
 //
 // Work item: one input block, its 11 frames summed in frame order by one workgroup.  Thread t owns
 // the pairs k = t + 256 r (r < 8): 16 sums per thread, bins k and 4096 - k (thread 0 holds bin 2048

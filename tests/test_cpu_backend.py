@@ -56,6 +56,29 @@ def test_cpu_parity(oracle, H, d, tb, lsb, rand, src):
     assert oracle.max_rel_err(y, ref) <= TOL
 
 
+TONES = [2045, 2046, 2046.4, 2047, 2047.5, 2048, 2049, 2050.6, 2051]   # 8192-point bins around fs/4
+REF_FLOAT_ERR = 2.6e-6   # the reference's float FFTW path against the f64 oracle
+
+
+@pytest.mark.parametrize("d,tb", [(0, 1024), (0, 2048), (1, 2048), (3, 1900), (6, 2048)])
+def test_cpu_tones_near_fs4(oracle, H, d, tb):
+    """A strong tone at the bins around 2048 (fs/4), in the passband, where the split's P = Hh (1 - i W)
+    vanishes: held to what the reference's own float path achieves against the f64 oracle, the
+    bar the GPU kernels are held to on the same tones (tests/test_gpu_fs4_tones.py).  The CPU
+    backend builds (P, Q) from a double W."""
+    from extio_sddc_amd.synth import make_tone_stream
+    nblk = 2
+    with _cpu(d, tb) as r:
+        for b0 in TONES:
+            x = make_tone_stream(nblk, b0)
+            r.TurnOn()
+            y = r.process(x[4096:])
+            ref = oracle.r2iq(x, nblk, d, tb, H=H)
+            assert np.max(np.abs(ref)) >= 10 ** (-40 / 20) * 1024 * 30000.0, (b0, "not in the passband")
+            err = oracle.max_rel_err(y, ref)
+            assert err <= REF_FLOAT_ERR, f"tone bin {b0}: {err:.3e}"
+
+
 def _sweep_cases():
     from test_gpu_sweep import _cases
     return _cases()

@@ -107,3 +107,25 @@ def test_fs_model_matches_oracle(tb, split):
     x = make_stream(1, "mix")
     y = M.r2iq_fs(x, 1, tb, H, perm, split)
     assert O.max_rel_err(y, O.r2iq(x, 1, 0, tb)) < 1e-12
+
+
+TONES = [2045, 2046, 2046.4, 2047, 2047.5, 2048, 2049, 2050.6, 2051]   # 8192-point bins around fs/4
+REF_FLOAT_ERR = 2.6e-6   # the reference's float FFTW path against the f64 oracle
+
+
+@pytest.mark.parametrize("tb", [1024, 2048])
+def test_fs_model_tones_near_fs4(tb):
+    """a strong tone at the bins around 2048, where P vanishes and r = Q / (i P) is large: the
+    model with the tables the kernel builds (W in double) within REF_FLOAT_ERR of the oracle (it
+    is a double model: it sits at rounding level); with the tables from the float W table, what
+    the kernel built before, the on-bin tones next to 2048 are wrong by more than that before any
+    float32 arithmetic"""
+    from extio_sddc_amd.synth import make_tone_stream
+    perm = np.array(P.read_header())
+    H = O.filter_bank(1.0)[0]
+    for b0 in TONES:
+        x = make_tone_stream(1, b0)
+        ref = O.r2iq(x, 1, 0, tb)
+        assert O.max_rel_err(M.r2iq_fs(x, 1, tb, H, perm), ref) <= REF_FLOAT_ERR, (tb, b0)
+        if b0 in (2045, 2046, 2047, 2049, 2051):
+            assert O.max_rel_err(M.r2iq_fs(x, 1, tb, H, perm, w_table="float"), ref) > REF_FLOAT_ERR, (tb, b0)

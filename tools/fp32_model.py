@@ -214,19 +214,49 @@ def forward(frames, rand=False, twmode="rec", plain=False, r0=0):
     return Z
 
 
-def split_filter(Z, d, tb, Hd, exact=False, form="pr"):
-    """T[m] (inverse input m < N) = Zk P + conj(Zc) Q, the table in double rounded once.
-    form "pr" (round 6, split_pr): P and r = Q / (i P) as float, T = P (Zk + i r conj Zc); bin 2048
-    (P = 0) holds r = 2^64, P = Q / (i 2^64).  "pq" (round 5, split_pq): the (P, Q) float4."""
+def split_coeffs(d, tb, Hd, w_table="double"):
+    """(ok, bb, P, Q, rr) of the inverse inputs m < N, in double: P = Hh (1 - i W), Q = Hh (1 + i W),
+    rr = Re[Q / (i P)] (0 where P = 0 or out of band).  w_table "double": W = e^{-2 pi i b / 8192}
+    in double, what the build kernels do (split_coeffs.h); "float": W rounded to complex64 first,
+    as the post8192 table the kernels read it from before: |W_f| != 1 makes Q / (i P) complex, and
+    the real part kept is wrong by 1e-5 at bins 2045..2051."""
+    if w_table not in ("double", "float"):
+        raise ValueError(w_table)
     N = HALF >> d
     m = np.arange(N)
     binv = tb + m - np.where(m >= N // 2, N, 0)
     ok = (binv >= 0) & (binv < HALF)
     bb = np.where(ok, binv, 0)
     Wb = np.exp(-2j * np.pi * bb / (2 * HALF))
+    if w_table == "float":
+        Wb = Wb.astype(np.complex64).astype(np.complex128)
     Hh = Hd[np.where(m < N // 2, m, HALF - N + m)] / 2   # the reference's H index (impl.hpp:90-94)
     P = np.where(ok, Hh * (1 - 1j * Wb), 0)
     Q = np.where(ok, Hh * (1 + 1j * Wb), 0)
+    sp = ok & (bb == HALF // 2)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rr = np.where(ok & ~sp, ((1 + 1j * Wb) / (1j * (1 - 1j * Wb))).real, 0.0)
+    return ok, bb, P, Q, rr
+
+
+def pr_tables(d, tb, Hd, w_table="double"):
+    """the float32 tables of the "pr" form, (ok, bb, P as complex of float32 values, r as float32):
+    bin 2048 (P = 0) holds r = 2^64, P = Q / (i 2^64)"""
+    ok, bb, P, Q, rr = split_coeffs(d, tb, Hd, w_table)
+    sp = ok & (bb == HALF // 2)
+    rr = np.where(sp, 2.0 ** 64, rr).astype(f32)
+    Pm = np.where(sp, Q / (1j * 2.0 ** 64), P)
+    return ok, bb, Pm.real.astype(f32).astype(f64) + 1j * Pm.imag.astype(f32).astype(f64), rr
+
+
+def split_filter(Z, d, tb, Hd, exact=False, form="pr", w_table="double"):
+    """T[m] (inverse input m < N) = Zk P + conj(Zc) Q, the table in double rounded once.
+    form "pr" (round 6, split_pr): P and r = Q / (i P) as float, T = P (Zk + i r conj Zc); bin 2048
+    (P = 0) holds r = 2^64, P = Q / (i 2^64).  "pq" (round 5, split_pq): the (P, Q) float4.
+    w_table: see split_coeffs (exact=True always takes the double W)."""
+    if exact:
+        w_table = "double"
+    ok, bb, P, Q, rr = split_coeffs(d, tb, Hd, w_table)
     zk = Z[:, bb]
     zc = Z[:, (HALF - bb) % HALF]
     if exact:
@@ -234,11 +264,7 @@ def split_filter(Z, d, tb, Hd, exact=False, form="pr"):
     zkx, zky = zk.real.astype(f32), zk.imag.astype(f32)
     zcx, zcy = zc.real.astype(f32), zc.imag.astype(f32)
     if form == "pr":
-        sp = ok & (bb == HALF // 2)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            rr = np.where(ok & ~sp, ((1 + 1j * Wb) / (1j * (1 - 1j * Wb))).real, 0.0)
-        rr = np.where(sp, 2.0 ** 64, rr).astype(f32)
-        Pm = np.where(sp, Q / (1j * 2.0 ** 64), P)
+        _, _, Pm, rr = pr_tables(d, tb, Hd, w_table)
         px, py = Pm.real.astype(f32), Pm.imag.astype(f32)
         vx, vy = fma(rr, zcy, zkx), fma(rr, zcx, zky)
         return fma(vx, px, -(vy * py)).astype(f64) + 1j * fma(vx, py, vy * px).astype(f64)
@@ -273,7 +299,7 @@ def inverse_tail(T, N):
 
 
 def r2iq_model(stream, nblk, d, tb, lsb, rand, Hd, twmode="rec", plain=False, exact_fwd=False, exact_inv=False,
-               exact_split=False, split_form="pr"):
+               exact_split=False, split_form="pr", w_table="double"):
     """frames -> forward -> split -> inverse -> overlap-discard, as the kernels (d >= 3 tails)"""
     N = HALF >> d
     idx = np.array([BLOCK * b + HOP * k for b in range(nblk) for k in range(FRAMES)])
@@ -287,7 +313,7 @@ def r2iq_model(stream, nblk, d, tb, lsb, rand, Hd, twmode="rec", plain=False, ex
     else:
         r0 = (((tb - N // 2) % HALF) >> 8) if N <= 1024 else 0   # the pruned kernel's rotation
         Z = forward(frames, rand, twmode, plain, r0)
-    T = split_filter(Z, d, tb, Hd, exact_split, split_form)
+    T = split_filter(Z, d, tb, Hd, exact_split, split_form, w_table)
     if exact_inv:
         y = np.fft.ifft(T, axis=1) * N
     else:

@@ -25,10 +25,15 @@ def dft16(a, sign):
     return a @ M
 
 
-def frame_fs(x8192, tb, H, perm, split="pr"):
+def frame_fs(x8192, tb, H, perm, split="pr", w_table="double"):
     """one d = 0 frame: 8192 real samples -> 4096 complex outputs (before overlap-discard).
     split "pq": F = Z P + conj(Zc) Q (round 5); "pr" (round 6): Q = i r P with r real, so
-    F = P (Z + i r conj(Zc)), except the bin 2048 (column 0, register 8: P = 0), F = Q conj(Z)"""
+    F = P (Z + i r conj(Zc)), except the bin 2048 (column 0, register 8: P = 0), F = Q conj(Z).
+    w_table "double": the tables from W in double (build_fs_tables_kernel, split_coeffs.h);
+    "float": from W rounded to complex64 (the post8192 table, what the kernel did before): r, the
+    real part of a ratio that is then complex, is wrong by 1e-5 at bins 2045..2051"""
+    if w_table not in ("double", "float"):
+        raise ValueError(w_table)
     z = x8192[0::2] + 1j * x8192[1::2]
     t = np.arange(256)
     # F0: butterfly t, inputs z[t + 256 r], out pos 16 t + k
@@ -50,6 +55,8 @@ def frame_fs(x8192, tb, H, perm, split="pr"):
     # split x filter, bin beta = c + 256 k, mirror from the partner lane l ^ 1, register 15 - k
     beta = (c[:, None] + 256 * r[None, :]) % HALF
     Wb = w(2 * HALF, beta)
+    if w_table == "float":
+        Wb = Wb.astype(np.complex64).astype(np.complex128)
     m = (beta - tb) % HALF
     valid = ((beta >= tb) & (beta - tb < HALF // 2)) | ((beta < tb) & (tb - beta <= HALF // 2))
     Hh = H[m] / 2
@@ -60,7 +67,7 @@ def frame_fs(x8192, tb, H, perm, split="pr"):
     # self-mirrored columns 0 and 128 (lanes 0 and 1): their own registers
     zc[0] = Zl[0][(16 - r) % 16]
     zc[1] = Zl[1][15 - r]
-    assert np.allclose(zc, Z[(-beta) % HALF])
+    assert np.allclose(zc, Z[(-beta) % HALF], atol=1e-6 * np.abs(Z).max())   # as above: a tone's empty bins
     if split == "pq":
         F = Zl * P + np.conj(zc) * Q
     else:
@@ -69,7 +76,8 @@ def frame_fs(x8192, tb, H, perm, split="pr"):
         sp = (beta == 2048)
         with np.errstate(divide="ignore", invalid="ignore"):
             rr = np.where(sp, 0.0, ((1 + 1j * Wb) / (1j * (1 - 1j * Wb))).real)
-        assert np.allclose(np.where(sp | ~valid, 0, Q - 1j * rr * P), 0, atol=1e-12 * np.abs(Q).max())
+        if w_table == "double":
+            assert np.allclose(np.where(sp | ~valid, 0, Q - 1j * rr * P), 0, atol=1e-12 * np.abs(Q).max())
         F = P * (Zl + 1j * rr * np.conj(zc))
         F[sp] = Q[sp] * np.conj(Zl[sp])
     # I0 (NS = 1): butterfly c, inputs F[c + 256 s], out pos 16 c + k
@@ -93,12 +101,12 @@ def frame_fs(x8192, tb, H, perm, split="pr"):
     return y
 
 
-def r2iq_fs(stream, nblk, tb, H, perm, split="pr"):
+def r2iq_fs(stream, nblk, tb, H, perm, split="pr", w_table="double"):
     out = np.empty(nblk * 32768, complex)
     for b in range(nblk):
         for k in range(FRAMES):
             s = b * BLOCK + k * HOP
-            y = frame_fs(stream[s:s + 2 * HALF].astype(np.float64), tb, H, perm, split)
+            y = frame_fs(stream[s:s + 2 * HALF].astype(np.float64), tb, H, perm, split, w_table)
             if k == 0:
                 out[b * 32768: b * 32768 + 2048] = y[1024:3072]
             else:
