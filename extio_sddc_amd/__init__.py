@@ -9,8 +9,11 @@ from .r2iq import (BBRF103_GAINFACTOR, BLOCK, FRAMES, HALF_FFT, NDEC, OUT_BLOCK,
 from .r2iq import (FFTN, SPECTRUM_BINS, WINDOW_BLACKMAN_HARRIS, WINDOW_HANN, WINDOW_RECT,  # noqa: F401
                    psd_to_dbfs, spectrum_window)
 from .r2iq import CHANNEL_SPECTRUM_SIZES, window  # noqa: F401
+from .r2iq import (CHANNEL_DECIMATE_TILE, DECIM_MAX_FACTOR, DECIM_MAX_TAPS,  # noqa: F401
+                   channel_decimate_samples)
 
 __all__ = ["R2iq", "DDCError", "DEVICE_CPU", "BACKEND_CPU", "BACKEND_HIP", "build", "load", "kaiser", "filter_taps", "filter_response",
            "channel_tuning", "device_count", "output_samples", "HALF_FFT", "BLOCK", "FRAMES", "NDEC", "OUT_BLOCK",
            "BBRF103_GAINFACTOR", "spectrum_window", "psd_to_dbfs", "FFTN", "SPECTRUM_BINS", "WINDOW_RECT", "WINDOW_HANN",
-           "WINDOW_BLACKMAN_HARRIS", "window", "CHANNEL_SPECTRUM_SIZES"]
+           "WINDOW_BLACKMAN_HARRIS", "window", "CHANNEL_SPECTRUM_SIZES", "channel_decimate_samples", "CHANNEL_DECIMATE_TILE",
+           "DECIM_MAX_TAPS", "DECIM_MAX_FACTOR"]

@@ -61,6 +61,11 @@ SIGNATURES = {
     "sddc_ddc_set_channel_spectrum_window": (_I, [_P, _P, _I]),
     "sddc_ddc_channel_spectrum_device": (_I, [_P, _P, _I, _SZ, _SZ, _I, _I, _I, _I, _P, _P]),
     "sddc_ddc_channel_spectrum_host": (_I, [_P, _P, _I, _SZ, _SZ, _I, _I, _I, _I, _P]),
+    "sddc_ddc_set_channel_decimator": (_I, [_P, _P, _I, _I, _I]),
+    "sddc_ddc_channel_decimator_reset": (_I, [_P]),
+    "sddc_ddc_channel_decimate_samples": (_SZ, [_I, _SZ]),
+    "sddc_ddc_channel_decimate_device": (_I, [_P, _P, _I, _SZ, _SZ, _P, _SZ, _P]),
+    "sddc_ddc_channel_decimate_host": (_I, [_P, _P, _I, _SZ, _SZ, _P, _SZ]),
     "sddc_ddc_register_host": (_I, [_P, _P, _SZ]),
     "sddc_ddc_unregister_host": (_I, [_P, _P]),
     # include/sddc_fft.h

@@ -320,5 +320,67 @@ void R2iq::channel_spectrum(const void *iq, bool cs16, int nch, size_t stride, i
     }
 }
 
+// The channel decimator (sddc_ddc_channel_decimate_host on a CPU handle).  Per channel the stream
+// [tail | the call's samples] is split into I and Q rows, and output m is the dot product of the
+// reversed taps g[k] = h[L - k] with the ntaps values from sample m R on: eight lane sums of
+// explicit FMAs over k = 8 i + lane, added in a fixed tree, then the last ntaps mod 8 taps one by
+// one.  The order depends on k alone, so any cut of a stream into calls gives the same bits.
+static inline float hsum8(__m256 v)
+{
+    const __m128 s4 = _mm_add_ps(_mm256_castps256_ps128(v), _mm256_extractf128_ps(v, 1));
+    const __m128 s2 = _mm_add_ps(s4, _mm_movehl_ps(s4, s4));
+    return _mm_cvtss_f32(_mm_add_ss(s2, _mm_shuffle_ps(s2, s2, 1)));
+}
+
+void R2iq::channel_decimate(const void *iq, bool cs16, float inv_s, int nch, size_t nsamp, size_t in_stride,
+                            const float *taps, int ntaps, int R, float *tail, float *out, size_t out_stride)
+{
+    const size_t L = (size_t)ntaps - 1, nout = nsamp / (size_t)R;
+    std::vector<float> g((size_t)ntaps), xr(L + nsamp), xi(L + nsamp);
+    for (int k = 0; k < ntaps; k++) g[(size_t)k] = taps[L - (size_t)k];
+    for (int c = 0; c < nch; c++) {
+        float *tl = tail + (size_t)c * L * 2;
+        for (size_t k = 0; k < L; k++) {
+            xr[k] = tl[2 * k];
+            xi[k] = tl[2 * k + 1];
+        }
+        if (cs16) {
+            const int16_t *x = static_cast<const int16_t *>(iq) + (size_t)c * in_stride;
+            for (size_t i = 0; i < nsamp; i++) {
+                xr[L + i] = (float)x[2 * i] * inv_s;
+                xi[L + i] = (float)x[2 * i + 1] * inv_s;
+            }
+        } else {
+            const float *x = static_cast<const float *>(iq) + (size_t)c * in_stride;
+            for (size_t i = 0; i < nsamp; i++) {
+                xr[L + i] = x[2 * i];
+                xi[L + i] = x[2 * i + 1];
+            }
+        }
+        float *y = out + (size_t)c * out_stride;
+        for (size_t m = 0; m < nout; m++) {
+            const float *pr = xr.data() + m * (size_t)R, *pi = xi.data() + m * (size_t)R;
+            __m256 ar = _mm256_setzero_ps(), ai = _mm256_setzero_ps();
+            int k = 0;
+            for (; k + 8 <= ntaps; k += 8) {
+                const __m256 gv = _mm256_loadu_ps(g.data() + k);
+                ar = _mm256_fmadd_ps(gv, _mm256_loadu_ps(pr + k), ar);
+                ai = _mm256_fmadd_ps(gv, _mm256_loadu_ps(pi + k), ai);
+            }
+            float sr = hsum8(ar), si = hsum8(ai);
+            for (; k < ntaps; k++) {
+                sr = std::fmaf(g[(size_t)k], pr[k], sr);
+                si = std::fmaf(g[(size_t)k], pi[k], si);
+            }
+            y[2 * m] = sr;
+            y[2 * m + 1] = si;
+        }
+        for (size_t k = 0; k < L; k++) {   // the last L values of [tail | samples]
+            tl[2 * k] = xr[nsamp + k];
+            tl[2 * k + 1] = xi[nsamp + k];
+        }
+    }
+}
+
 }  // namespace cpu
 }  // namespace sddc

@@ -67,6 +67,13 @@ public:
     // psd[c][r][q] = scale x the sum over the row's frames, in frame order, of |X_f[(q + n/2) mod n]|^2.
     void channel_spectrum(const void *iq, bool cs16, int nch, size_t stride, int n, int hop, int fpr, int nrows,
                           const float *w, float scale, float *psd);
+    // The channel decimator (sddc_ddc.h, sddc_ddc_channel_decimate_host): y_c[m] = sum_j taps[j]
+    // x_c[m R - j] on nch streams (cs16: int16 (I, Q) read as v * inv_s, else float (I, Q)), channel c
+    // at c * in_stride components, nsamp = a multiple of R samples each; channel c's nsamp / R
+    // (I, Q) float outputs at out + c * out_stride floats.  tail: [nch][ntaps - 1][2] floats, each
+    // channel's last sample values before the call, replaced by those after it.  Stateless otherwise.
+    static void channel_decimate(const void *iq, bool cs16, float inv_s, int nch, size_t nsamp, size_t in_stride,
+                                 const float *taps, int ntaps, int R, float *tail, float *out, size_t out_stride);
 
 private:
     struct Buf;

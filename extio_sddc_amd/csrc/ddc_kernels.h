@@ -190,6 +190,34 @@ hipError_t launch_channel_spectrum(const KernelTables &t, const void *d_iq, int 
                                    size_t stride_samples, int n, int hop, int fpr, float *d_psd,
                                    const float *d_window, float scale, int max_wgs, int device, hipStream_t s);
 
+// Channel decimator (ddc_channel_decimate.hip, sddc_ddc_channel_decimate_device): y_c[m] =
+// sum_j h[j] x_c[m R - j] on nch streams in the DDC's output format (cs16: int16 (I, Q) pairs read
+// as v * (float)(1 / cs16_scale), else float pairs), channel c at d_iq + c * in_stride components,
+// nsamp = a multiple of R samples each; channel c's nsamp / R float2 outputs at d_out + c *
+// out_stride floats (8-byte aligned).  d_taps: the ntaps taps in the kernel's order
+// (channel_decimate_order_taps: by phase of the polyphase rows).  d_tail_in: [nch][ntaps - 1] float2,
+// each channel's last sample values before this call; d_tail_out: the same after it (another
+// buffer; both may be null when ntaps == 1).  One work item per (channel, tile of at most
+// kChDecTile outputs); max_wgs > 0 caps the grid (tests).  The caller has checked the strides.
+constexpr int kChDecTile = 512;        // outputs per tile (two per thread), when the LDS holds them
+constexpr int kChDecLds = 4864;        // float2 slots of LDS per tile (+ 256 of slack: 40 KiB, 4 workgroups per CU)
+constexpr int kChDecPitchPad = 15;     // the pitch search's range above the rows needed
+constexpr int kChDecMaxTaps = 1024;    // SDDC_DDC_DECIM_MAX_TAPS
+constexpr int kChDecMaxFactor = 64;    // SDDC_DDC_DECIM_MAX_FACTOR
+static_assert(kChDecLds / kChDecMaxFactor - kChDecPitchPad - (kChDecMaxTaps - 2 + kChDecMaxFactor) / kChDecMaxFactor >= 1,
+              "a tile of both maxima holds an output");
+// The tile of (R, ntaps): its outputs (kChDecTile, or what the LDS holds beside the halo's rows), the
+// polyphase rows' pitch and the modelled extra LDS cycles of the stage's four stores per wave.
+struct ChDecLayout {
+    int tile = 0, pitch = 0, store_conflicts = 0;
+};
+ChDecLayout channel_decimate_layout(int R, int ntaps, int cs16);
+void channel_decimate_order_taps(const float *h, int ntaps, int R, float *g /* [ntaps] */);
+hipError_t launch_channel_decimate(const KernelTables &t, const void *d_iq, int cs16, float cs16_scale, int nch,
+                                   size_t nsamp, size_t in_stride, const float *d_taps, int ntaps, int R,
+                                   const float2 *d_tail_in, float2 *d_tail_out, float *d_out, size_t out_stride,
+                                   int max_wgs, int device, hipStream_t s);
+
 // batched FFTs (fft_batch.hip, include/sddc_fft.h); fft_prepare fills the device's twiddle
 // table once (synchronises s the first time)
 hipError_t fft_prepare(hipStream_t s);

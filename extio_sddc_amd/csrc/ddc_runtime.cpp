@@ -300,6 +300,23 @@ struct sddc_ddc {
     Readers chsp_readers;
     int chsp_max_wgs = 0;                  // SDDC_DDC_PARAM_CHSPEC_MAX_WGS
 
+    // channel decimator (sddc_ddc_channel_decimate_*): the taps (empty = off) with the factor and the
+    // channel count, their device copy, and each channel's last ntaps - 1 sample values as float2 in
+    // two device buffers: a launch reads d_chdec_tail[chdec_cur] and writes the other one, and the
+    // host swaps them after it.  The tails are per handle, so every launch first waits for the other
+    // streams' last launches (chdec_readers).  A CPU handle keeps the tails in chdec_tail_h.
+    std::vector<float> chdec_taps;
+    int chdec_R = 0, chdec_nch = 0;
+    float *d_chdec_taps = nullptr;         // [SDDC_DDC_DECIM_MAX_TAPS]
+    float2 *d_chdec_tail[2] = {};          // [chdec_nch][ntaps - 1] each
+    int chdec_cur = 0;
+    std::vector<float> chdec_tail_h;       // CPU handle: [chdec_nch][ntaps - 1][2]
+    void *d_chdec_in = nullptr;            // channel_decimate_host
+    float *d_chdec_out = nullptr;
+    size_t chdec_in_cap = 0, chdec_out_cap = 0;   // bytes, floats
+    Readers chdec_readers;
+    int chdec_max_wgs = 0;                 // SDDC_DDC_PARAM_CHDEC_MAX_WGS
+
     // CPU handle (device SDDC_DDC_DEVICE_CPU): the AVX2 backend; no HIP object above exists
     std::unique_ptr<sddc::cpu::R2iq> cpu;
 
@@ -515,6 +532,7 @@ int sddc_ddc_destroy(sddc_ddc_t *h)
         (void)h->ch_readers.sync();
         (void)h->sp_readers.sync();
         (void)h->chsp_readers.sync();
+        (void)h->chdec_readers.sync();
         if (h->d_tables) (void)hipFree(h->d_tables);
         for (auto &sl : h->hs) {
             if (sl.d_in) (void)hipFree(sl.d_in);
@@ -546,6 +564,12 @@ int sddc_ddc_destroy(sddc_ddc_t *h)
         if (h->d_chsp_in) (void)hipFree(h->d_chsp_in);
         if (h->d_chsp_out) (void)hipFree(h->d_chsp_out);
         h->chsp_readers.clear();
+        if (h->d_chdec_taps) (void)hipFree(h->d_chdec_taps);
+        for (float2 *p : h->d_chdec_tail)
+            if (p) (void)hipFree(p);
+        if (h->d_chdec_in) (void)hipFree(h->d_chdec_in);
+        if (h->d_chdec_out) (void)hipFree(h->d_chdec_out);
+        h->chdec_readers.clear();
         if (h->fsa.h_ring) (void)hipHostFree(h->fsa.h_ring);   // its writers were waited for above
         h->readers.clear();
         h->ch_readers.clear();
@@ -1059,6 +1083,10 @@ int sddc_ddc_internal_set_param(sddc_ddc_t *h, int param, int value)
     case SDDC_DDC_PARAM_CHSPEC_MAX_WGS:
         if (value < 0) return fail(SDDC_ERR_ARG, "channel spectrum workgroup cap %d is negative", value);
         h->chsp_max_wgs = value;
+        return SDDC_OK;
+    case SDDC_DDC_PARAM_CHDEC_MAX_WGS:
+        if (value < 0) return fail(SDDC_ERR_ARG, "channel decimator workgroup cap %d is negative", value);
+        h->chdec_max_wgs = value;
         return SDDC_OK;
     default:
         return fail(SDDC_ERR_ARG, "unknown parameter %d", param);
@@ -1597,6 +1625,235 @@ int sddc_ddc_channel_spectrum_host(sddc_ddc_t *h, const void *iq, int nch, size_
     const int rc = chsp_launch(h, h->d_chsp_in, nch, in_stride, n, hop, frames_per_row, nrows, h->d_chsp_out, h->stream);
     if (rc == SDDC_OK)
         HIP_TRY(hipMemcpyAsync(psd, h->d_chsp_out, out_floats * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // also after a failed launch: the caller's input is free again
+    return rc;
+}
+
+/* ---- channel decimator: a streaming decimating FIR on the DDC's IQ output ----------------- */
+static_assert(SDDC_DDC_DECIM_MAX_TAPS == sddc::kChDecMaxTaps && SDDC_DDC_DECIM_MAX_FACTOR == sddc::kChDecMaxFactor,
+              "the kernel's limits are the ABI's");
+
+// off: no taps, no tails (the caller holds h->mu and has waited for the launches in flight)
+static void chdec_clear(sddc_ddc_t *h)
+{
+    h->chdec_taps.clear();
+    h->chdec_R = h->chdec_nch = 0;
+    h->chdec_tail_h.clear();
+    for (float2 *&p : h->d_chdec_tail) {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+    }
+    h->chdec_cur = 0;
+}
+
+/* internal (sddc_ddc_internal.h): the kernel's tile of (factor, ntaps, format) */
+int sddc_ddc_internal_chdec_layout(int factor, int ntaps, int cs16, int *tile, int *pitch, int *store_conflicts)
+{
+    if (factor < 2 || factor > SDDC_DDC_DECIM_MAX_FACTOR || ntaps < 1 || ntaps > SDDC_DDC_DECIM_MAX_TAPS || !tile ||
+        !pitch || !store_conflicts)
+        return fail(SDDC_ERR_ARG, "chdec layout: factor %d, ntaps %d or a null pointer", factor, ntaps);
+    const sddc::ChDecLayout g = sddc::channel_decimate_layout(factor, ntaps, cs16);
+    *tile = g.tile;
+    *pitch = g.pitch;
+    *store_conflicts = g.store_conflicts;
+    return SDDC_OK;
+}
+
+int sddc_ddc_set_channel_decimator(sddc_ddc_t *h, const float *taps, int ntaps, int factor, int nch)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    const bool off = !taps || ntaps == 0;
+    if (!off) {
+        if (ntaps < 1 || ntaps > SDDC_DDC_DECIM_MAX_TAPS)
+            return fail(SDDC_ERR_ARG, "channel decimator: ntaps %d outside 1..%d", ntaps, SDDC_DDC_DECIM_MAX_TAPS);
+        if (factor < 2 || factor > SDDC_DDC_DECIM_MAX_FACTOR)
+            return fail(SDDC_ERR_ARG, "channel decimator: factor %d outside 2..%d", factor, SDDC_DDC_DECIM_MAX_FACTOR);
+        if (nch < 1 || nch > SDDC_DDC_MAX_CHANNELS)
+            return fail(SDDC_ERR_ARG, "channel decimator: nch %d outside 1..%d", nch, SDDC_DDC_MAX_CHANNELS);
+        for (int j = 0; j < ntaps; j++)
+            if (!std::isfinite(taps[j])) return fail(SDDC_ERR_ARG, "channel decimator: tap %d is not finite", j);
+    }
+    std::lock_guard<std::mutex> lk(h->mu);
+    const size_t tail = off ? 0 : (size_t)nch * (size_t)(ntaps - 1);   // complex values
+    if (h->cpu) {
+        chdec_clear(h);
+        if (off) return SDDC_OK;
+        try {
+            h->chdec_tail_h.assign(2 * tail, 0.f);
+            h->chdec_taps.assign(taps, taps + ntaps);
+        } catch (const std::exception &ex) {
+            chdec_clear(h);
+            return fail(SDDC_ERR_NOMEM, "channel decimator: %s", ex.what());
+        }
+        h->chdec_R = factor;
+        h->chdec_nch = nch;
+        return SDDC_OK;
+    }
+    DeviceGuard g(h->device);
+    HIP_TRY(g.err);
+    HIP_TRY(h->chdec_readers.sync());   // earlier launches, on any stream, may still use the taps and the tails
+    chdec_clear(h);                     // a failed upload leaves the decimator off
+    if (off) return SDDC_OK;
+    if (!h->d_chdec_taps) HIP_TRY(hipMalloc(&h->d_chdec_taps, SDDC_DDC_DECIM_MAX_TAPS * sizeof(float)));
+    {   // the device copy is in the kernel's order
+        float ordered[SDDC_DDC_DECIM_MAX_TAPS];
+        sddc::channel_decimate_order_taps(taps, ntaps, factor, ordered);
+        HIP_TRY(hipMemcpy(h->d_chdec_taps, ordered, (size_t)ntaps * sizeof(float), hipMemcpyHostToDevice));
+    }
+    if (tail) {
+        for (float2 *&p : h->d_chdec_tail) {
+            if (hipMalloc(&p, tail * sizeof(float2)) != hipSuccess) {
+                (void)hipGetLastError();
+                p = nullptr;
+                chdec_clear(h);
+                return fail(SDDC_ERR_NOMEM, "channel decimator: no device memory for %zu tail values", tail);
+            }
+        }
+        // zeroed on the handle's stream and waited for: the first launch may be on any stream
+        hipError_t e = hipMemsetAsync(h->d_chdec_tail[0], 0, tail * sizeof(float2), h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) {
+            chdec_clear(h);
+            HIP_TRY(e);
+        }
+    }
+    h->chdec_taps.assign(taps, taps + ntaps);
+    h->chdec_R = factor;
+    h->chdec_nch = nch;
+    return SDDC_OK;
+}
+
+int sddc_ddc_channel_decimator_reset(sddc_ddc_t *h)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->chdec_taps.empty()) return fail(SDDC_ERR_STATE, "channel decimator reset: no decimator set");
+    if (h->cpu) {
+        std::fill(h->chdec_tail_h.begin(), h->chdec_tail_h.end(), 0.f);
+        return SDDC_OK;
+    }
+    const size_t tail = (size_t)h->chdec_nch * (h->chdec_taps.size() - 1);
+    if (!tail) return SDDC_OK;
+    DeviceGuard g(h->device);
+    HIP_TRY(g.err);
+    HIP_TRY(h->chdec_readers.sync());   // earlier launches, on any stream, may still use the tails
+    HIP_TRY(hipMemsetAsync(h->d_chdec_tail[h->chdec_cur], 0, tail * sizeof(float2), h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // the next launch may be on any stream
+    return SDDC_OK;
+}
+
+size_t sddc_ddc_channel_decimate_samples(int factor, size_t nsamp)
+{
+    if (factor < 2 || factor > SDDC_DDC_DECIM_MAX_FACTOR || nsamp % (size_t)factor != 0) return 0;
+    return nsamp / (size_t)factor;
+}
+
+// the checks both calls share (under h->mu: the format and the decimator are read here)
+static int check_chdec_args(const sddc_ddc_t *h, const void *iq, int nch, size_t nsamp, size_t in_stride,
+                            const float *out, size_t out_stride)
+{
+    if (h->chdec_taps.empty()) return fail(SDDC_ERR_STATE, "channel decimate: no decimator set");
+    if (nch != h->chdec_nch)
+        return fail(SDDC_ERR_STATE, "channel decimate: the decimator is set for %d channels, the call has %d",
+                    h->chdec_nch, nch);
+    const size_t R = (size_t)h->chdec_R;
+    if (nsamp == 0 || nsamp % R != 0 || nsamp > ((size_t)1 << 40))
+        return fail(SDDC_ERR_ARG, "nsamp must be a positive multiple of the factor %zu, at most 2^40 (got %zu)", R, nsamp);
+    if (nch > 1 && (in_stride < 2 * nsamp || (in_stride & 1) != 0))
+        return fail(SDDC_ERR_ARG, "in_stride must be even and >= 2 nsamp (got %zu, nsamp %zu)", in_stride, nsamp);
+    if (nch > 1 && (out_stride < 2 * (nsamp / R) || (out_stride & 1) != 0))
+        return fail(SDDC_ERR_ARG, "out_stride must be even and >= 2 nsamp / factor (got %zu, need %zu)", out_stride,
+                    2 * (nsamp / R));
+    if (!iq || !out) return fail(SDDC_ERR_ARG, "null buffer");
+    const uintptr_t sample = h->out_fmt == SDDC_DDC_FMT_CS16 ? 4 : 8;
+    if (((uintptr_t)iq & (sample - 1)) != 0) return fail(SDDC_ERR_ARG, "iq must be %d-byte aligned", (int)sample);
+    if (((uintptr_t)out & 7) != 0) return fail(SDDC_ERR_ARG, "the output must be 8-byte aligned");
+    return SDDC_OK;
+}
+
+// One launch on s: it reads the current tails and writes the other buffer, so it runs after every
+// earlier launch of the handle, whatever its stream; the buffers swap once it is enqueued.
+static int chdec_launch(sddc_ddc_t *h, const void *d_iq, int nch, size_t nsamp, size_t in_stride, float *d_out,
+                        size_t out_stride, hipStream_t s)
+{
+    HIP_TRY(h->chdec_readers.order_before(s));
+    const int cur = h->chdec_cur;
+    const hipError_t e = sddc::launch_channel_decimate(h->tables, d_iq, h->out_fmt == SDDC_DDC_FMT_CS16, h->cs16_scale,
+                                                       nch, nsamp, in_stride, h->d_chdec_taps, (int)h->chdec_taps.size(),
+                                                       h->chdec_R, h->d_chdec_tail[cur], h->d_chdec_tail[cur ^ 1], d_out,
+                                                       out_stride, h->chdec_max_wgs, h->device, s);
+    const hipError_t er = h->chdec_readers.record(s);   // whatever was enqueued stays ordered
+    HIP_TRY(e);
+    h->chdec_cur = cur ^ 1;
+    HIP_TRY(er);
+    return SDDC_OK;
+}
+
+int sddc_ddc_channel_decimate_device(sddc_ddc_t *h, const void *d_iq, int nch, size_t nsamp, size_t in_stride,
+                                     float *d_out, size_t out_stride, void *hip_stream)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(h->mu);   // the call reads the format and the decimator: one consistent set
+    if (h->cpu) return fail(SDDC_ERR_STATE, "channel_decimate_device: a CPU handle has no device path");
+    if (int rc = check_chdec_args(h, d_iq, nch, nsamp, in_stride, d_out, out_stride)) return rc;
+    DeviceGuard g(h->device);
+    HIP_TRY(g.err);
+    return chdec_launch(h, d_iq, nch, nsamp, in_stride, d_out, out_stride, (hipStream_t)hip_stream);
+}
+
+int sddc_ddc_channel_decimate_host(sddc_ddc_t *h, const void *iq, int nch, size_t nsamp, size_t in_stride, float *out,
+                                   size_t out_stride)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (int rc = check_chdec_args(h, iq, nch, nsamp, in_stride, out, out_stride)) return rc;
+    const bool cs16 = h->out_fmt == SDDC_DDC_FMT_CS16;
+    const size_t nout = nsamp / (size_t)h->chdec_R;
+    if (h->cpu) {
+        try {
+            sddc::cpu::R2iq::channel_decimate(iq, cs16, (float)(1.0 / (double)h->cs16_scale), nch, nsamp,
+                                              nch > 1 ? in_stride : 0, h->chdec_taps.data(), (int)h->chdec_taps.size(),
+                                              h->chdec_R, h->chdec_tail_h.data(), out, nch > 1 ? out_stride : 0);
+        } catch (const std::exception &ex) {   // thrown before any output or tail is written
+            return fail(SDDC_ERR_NOMEM, "cpu backend: %s", ex.what());
+        }
+        return SDDC_OK;
+    }
+    DeviceGuard g(h->device);
+    HIP_TRY(g.err);
+    // the spans that hold every channel's samples and outputs
+    const size_t in_bytes = ((size_t)(nch - 1) * (nch > 1 ? in_stride : 0) + 2 * nsamp) * (cs16 ? 2 : 4);
+    const size_t out_floats = (size_t)(nch - 1) * (nch > 1 ? out_stride : 0) + 2 * nout;
+    // the earlier host calls were synchronous: nothing reads the old buffers
+    if (in_bytes > h->chdec_in_cap) {
+        if (h->d_chdec_in) (void)hipFree(h->d_chdec_in);
+        h->d_chdec_in = nullptr;
+        h->chdec_in_cap = 0;
+        if (hipMalloc(&h->d_chdec_in, in_bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(SDDC_ERR_NOMEM, "channel_decimate_host: no device memory for %zu input bytes", in_bytes);
+        }
+        h->chdec_in_cap = in_bytes;
+    }
+    if (out_floats > h->chdec_out_cap) {
+        if (h->d_chdec_out) (void)hipFree(h->d_chdec_out);
+        h->d_chdec_out = nullptr;
+        h->chdec_out_cap = 0;
+        if (hipMalloc(&h->d_chdec_out, out_floats * sizeof(float)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(SDDC_ERR_NOMEM, "channel_decimate_host: no device memory for %zu output floats", out_floats);
+        }
+        h->chdec_out_cap = out_floats;
+    }
+    HIP_TRY(hipMemcpyAsync(h->d_chdec_in, iq, in_bytes, hipMemcpyHostToDevice, h->stream));
+    const int rc = chdec_launch(h, h->d_chdec_in, nch, nsamp, in_stride, h->d_chdec_out, out_stride, h->stream);
+    if (rc == SDDC_OK) {   // the streams alone: the caller's memory between them stays as it is
+        if (nch == 1 || out_stride == 2 * nout)
+            HIP_TRY(hipMemcpyAsync(out, h->d_chdec_out, out_floats * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        else
+            HIP_TRY(hipMemcpy2DAsync(out, out_stride * sizeof(float), h->d_chdec_out, out_stride * sizeof(float),
+                                     2 * nout * sizeof(float), (size_t)nch, hipMemcpyDeviceToHost, h->stream));
+    }
     HIP_TRY(hipStreamSynchronize(h->stream));   // also after a failed launch: the caller's input is free again
     return rc;
 }

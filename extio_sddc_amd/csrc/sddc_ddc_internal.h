@@ -54,6 +54,11 @@ extern "C" {
  * enough workgroups for all items, or full residency with a loop.  The grid changes no output bit
  * (tests). */
 #define SDDC_DDC_PARAM_CHSPEC_MAX_WGS 12
+/* SDDC_DDC_PARAM_CHDEC_MAX_WGS = n > 0: the channel decimator kernel's grid is at most n workgroups,
+ * so a workgroup takes several rounds of (channel, tile) items and the items outnumber the
+ * workgroups; 0 (default): one workgroup per item, or full residency with a loop.  The grid changes
+ * no output bit (tests). */
+#define SDDC_DDC_PARAM_CHDEC_MAX_WGS 13
 
 int sddc_ddc_internal_set_param(sddc_ddc_t *h, int param, int value);
 /* A given table of n relative shares (n = the d = 0 kernel's full-residency grid, 4 x CUs) used as
@@ -63,6 +68,10 @@ int sddc_ddc_internal_fs_set_shares(sddc_ddc_t *h, const float *shares, int n);
  * skipped, the last d = 0 launch took a share table, the last d = 0 launch was measured}; counts
  * receives the current table's frames per workgroup.  Returns the number of counts written. */
 int sddc_ddc_internal_fs_split_state(sddc_ddc_t *h, long *info, int *counts, int ncounts);
+/* The channel decimator kernel's tile of (factor, ntaps, format): outputs per tile, the polyphase
+ * rows' pitch in float2 slots, and the modelled extra LDS cycles of the stage's stores per wave
+ * (tools/channel_decimate_banks.py; no handle, no device).  SDDC_ERR_ARG outside the ABI's ranges. */
+int sddc_ddc_internal_chdec_layout(int factor, int ntaps, int cs16, int *tile, int *pitch, int *store_conflicts);
 /* The controller alone (no handle, no device): tests/test_adaptive_split.py. */
 void *sddc_fs_split_create(int G, unsigned slot_weights);
 void sddc_fs_split_destroy(void *c);

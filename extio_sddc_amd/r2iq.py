@@ -103,6 +103,19 @@ def window(kind, n: int) -> np.ndarray:
     return w
 
 
+DECIM_MAX_TAPS = 1024       # SDDC_DDC_DECIM_MAX_TAPS
+DECIM_MAX_FACTOR = 64       # SDDC_DDC_DECIM_MAX_FACTOR
+CHANNEL_DECIMATE_TILE = 512  # ddc_kernels.h kChDecTile: the decimator kernel's outputs per tile
+
+
+def channel_decimate_samples(factor: int, nsamp: int) -> int:
+    """Outputs per channel of a channel_decimate call: nsamp / factor, 0 if the factor is outside
+    2..64 or does not divide nsamp (sddc_ddc_channel_decimate_samples)."""
+    if nsamp < 0:
+        return 0
+    return int(_lib.load().sddc_ddc_channel_decimate_samples(int(factor), int(nsamp)))
+
+
 def psd_to_dbfs(psd) -> np.ndarray:
     """R2iq.spectrum's output in dB relative to a full-scale real tone (amplitude 32768 reads
     32768^2 / 4 at its bin centre): 10 log10(4 psd / 32768^2); -inf where psd is 0."""
@@ -129,6 +142,7 @@ class R2iq:
         self._rand = False
         self._lsb = False
         self._fmt = FMT_CF32
+        self._decim = None   # (ntaps, factor, nch) of setChannelDecimator
 
     # -- lifecycle --------------------------------------------------------
     @property
@@ -376,6 +390,78 @@ class R2iq:
         check(self._L.sddc_ddc_channel_spectrum_device(self._h, d_iq.data_ptr(), nch, nsamp, in_stride, n, hop,
                                                        frames_per_row, nrows, d_psd.data_ptr(),
                                                        _stream_handle(stream)))
+
+    # -- channel decimator ------------------------------------------------------
+    def setChannelDecimator(self, taps, factor: int = 0, nch: int = 0) -> None:
+        """The streaming decimating FIR of channel_decimate: real taps (1..1024, e.g. from kaiser),
+        an integer factor 2..64 and the channel count of the calls that follow.  Every call zeroes
+        the kept stream tails.  None or no taps turns the decimator off.  Output m of a channel is
+        sum_j taps[j] x[m * factor - j]: the group delay of symmetric taps is (ntaps - 1) / 2 input
+        samples."""
+        if taps is None or len(taps) == 0:
+            check(self._L.sddc_ddc_set_channel_decimator(self._h, None, 0, 0, 0))
+            self._decim = None
+            return
+        t = np.ascontiguousarray(np.asarray(taps, np.float32).reshape(-1))
+        check(self._L.sddc_ddc_set_channel_decimator(self._h, t.ctypes.data, t.size, int(factor), int(nch)))
+        self._decim = (t.size, int(factor), int(nch))
+
+    def resetChannelDecimator(self) -> None:
+        """Zero every channel's tail: the next channel_decimate call starts a new stream."""
+        check(self._L.sddc_ddc_channel_decimator_reset(self._h))
+
+    def channel_decimate(self, iq: np.ndarray) -> np.ndarray:
+        """The decimator on host arrays: iq is complex64 [nch, nsamp] (CF32) or int16 [nch, nsamp, 2]
+        (CS16), matching the handle's output format, nsamp a multiple of the factor; a single stream
+        may drop the channel axis.  Returns complex64 [nch, nsamp / factor] and keeps each
+        channel's last ntaps - 1 samples for the next call."""
+        if self._decim is None:
+            raise DDCError(-4, "no channel decimator set")
+        iq = np.asarray(iq)
+        if self._fmt == FMT_CS16:
+            if iq.dtype != np.int16 or iq.ndim not in (2, 3) or iq.shape[-1] != 2:
+                raise DDCError(-1, "CS16 handle: iq must be int16 [nch, nsamp, 2]")
+            iq = np.ascontiguousarray(iq.reshape((1,) + iq.shape if iq.ndim == 2 else iq.shape))
+        else:
+            if iq.dtype != np.complex64 or iq.ndim not in (1, 2):
+                raise DDCError(-1, "CF32 handle: iq must be complex64 [nch, nsamp]")
+            iq = np.ascontiguousarray(iq.reshape(1, -1) if iq.ndim == 1 else iq)
+        nch, nsamp = iq.shape[0], iq.shape[1]
+        nout = channel_decimate_samples(self._decim[1], nsamp)
+        if nout == 0:
+            raise DDCError(-1, f"nsamp {nsamp} must be a positive multiple of the factor {self._decim[1]}")
+        out = np.empty((nch, nout), np.complex64)
+        check(self._L.sddc_ddc_channel_decimate_host(self._h, iq.ctypes.data, nch, nsamp, 2 * nsamp, out.ctypes.data,
+                                                     2 * nout))
+        return out
+
+    def channel_decimate_device(self, d_iq, nch: int, nsamp: int, in_stride: int, d_out, out_stride: int,
+                                stream=None) -> None:
+        """The decimator on the buffer process_device / process_channels_device wrote: d_iq is a
+        float32 (CS16: int16) device tensor, channel c at c * in_stride components, nsamp complex
+        samples each; d_out float32, channel c's nsamp / factor (I, Q) pairs at c * out_stride
+        floats.  Enqueued on `stream` like process_device; the calls of one handle run in call order."""
+        import torch
+        if self._decim is None:
+            raise DDCError(-4, "no channel decimator set")
+        if not (d_iq.is_cuda and d_out.is_cuda):
+            raise DDCError(-1, "device path needs device tensors")
+        want = torch.int16 if self._fmt == FMT_CS16 else torch.float32
+        if d_iq.dtype != want or d_out.dtype != torch.float32:
+            raise DDCError(-1, f"d_iq must be {want} and d_out float32")
+        if not (d_iq.is_contiguous() and d_out.is_contiguous()):
+            raise DDCError(-1, "tensors must be contiguous")
+        nout = channel_decimate_samples(self._decim[1], nsamp)
+        if nch < 1 or nout == 0:
+            raise DDCError(-1, f"nch must be >= 1 and nsamp {nsamp} a positive multiple of the factor {self._decim[1]}")
+        need = (nch - 1) * in_stride + 2 * nsamp
+        if d_iq.numel() < need:
+            raise DDCError(-1, f"d_iq has {d_iq.numel()} components, need {need}")
+        need = (nch - 1) * out_stride + 2 * nout
+        if d_out.numel() < need:
+            raise DDCError(-1, f"d_out has {d_out.numel()} floats, need {need}")
+        check(self._L.sddc_ddc_channel_decimate_device(self._h, d_iq.data_ptr(), nch, nsamp, in_stride,
+                                                       d_out.data_ptr(), out_stride, _stream_handle(stream)))
 
 
 def _check_device_buffers(d_in, nblk, d_out, out_floats, fmt=0):

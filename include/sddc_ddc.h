@@ -48,7 +48,10 @@ extern "C" {
                                        still 3: + spectrum_window, set_spectrum_window, spectrum_device,
                                        spectrum_host (new symbols only);
                                        still 3: + window, set_channel_spectrum_window,
-                                       channel_spectrum_device, channel_spectrum_host (new symbols only) */
+                                       channel_spectrum_device, channel_spectrum_host (new symbols only);
+                                       still 3: + set_channel_decimator, channel_decimator_reset,
+                                       channel_decimate_samples, channel_decimate_device,
+                                       channel_decimate_host (new symbols only) */
 
 #define SDDC_DDC_HALF_FFT   4096    /* halfFft               fft_mt_r2iq.h:18 */
 #define SDDC_DDC_FFTN       8192    /* FFTN_R_ADC            config.h:49 */
@@ -285,6 +288,58 @@ int sddc_ddc_channel_spectrum_device(sddc_ddc_t *h, const void *d_iq, int nch, s
  * backend's FFT of n points, the same definition with the same single final scale. */
 int sddc_ddc_channel_spectrum_host(sddc_ddc_t *h, const void *iq, int nch, size_t nsamp, size_t in_stride,
                                    int n, int hop, int frames_per_row, int nrows, float *psd);
+
+/* ---- channel decimator: a streaming second-stage FIR for narrowband channels --------------
+ * An integer-factor decimating FIR with real taps, applied independently to every channel stream
+ * of the DDC's output: the step between process_channels_device (1 MS/s per channel at d = 6 of a
+ * 128 MS/s ADC) and a narrowband demodulator (a few tens of kS/s).  For channel c, the taps
+ * h[0..ntaps-1] and the factor R:
+ *   v_c[i] = sum_{j < ntaps} h[j] x_c[i - j]       i = stream index since the last set or reset
+ *   y_c[m] = v_c[m*R]                               m = 0, 1, 2, ...
+ * with x_c[i] = 0 for i < 0.  A call consumes nsamp samples per channel and produces nsamp / R
+ * outputs; the handle keeps the last ntaps-1 sample values of each channel as float32 (on the
+ * device for a GPU handle, on the host for a CPU handle) and the next call continues the stream.
+ * nsamp is a positive multiple of R, so the decimation phase never moves (the DDC's output
+ * lengths nblk*(32768>>d) make every power of two trivial).  The group delay is (ntaps-1)/2 input
+ * samples, (ntaps-1)/(2R) output samples, for symmetric taps; y_c[0] is the response to x_c[0]
+ * alone through h[0].
+ * Input: as for the channel spectrum, channel c starts c*in_stride components into the buffer
+ * (for nch > 1 in_stride is even and >= 2*nsamp), the base pointer is aligned to one complex
+ * sample, and the buffer is read in the handle's CURRENT output format: CF32 the float pair as
+ * stored, CS16 x = (float)v * inv_s with inv_s = (float)(1.0 / (double)cs16_scale).  The kept
+ * values are sample values, not codes, so the format may change between calls.
+ * Output: CF32; channel c's nsamp/R complex samples start c*out_stride floats into the output
+ * (for nch > 1 out_stride is even and >= 2*nsamp/R), which is 8-byte aligned.  Nothing is written
+ * between the streams or outside them.
+ * A stored output depends only on its ntaps sample values and the taps, through a sequence of
+ * float operations fixed by the tap index (no atomics): it is bit-identical from run to run, on any
+ * stream, for any grid, for a channel alone or among others, and for one call of N samples
+ * against any cut of the same samples into several calls.  Each component is within
+ * gamma * sum_j |h[j]| |x[mR - j]|, gamma = n u / (1 - n u), n = ntaps + 1, u = 2^-24, of the exact sum. */
+#define SDDC_DDC_DECIM_MAX_TAPS   1024
+#define SDDC_DDC_DECIM_MAX_FACTOR 64
+/* taps: host array of ntaps floats (1..1024, all finite), 2 <= factor <= 64, 1 <= nch <=
+ * SDDC_DDC_MAX_CHANNELS; a violation returns SDDC_ERR_ARG.  NULL or ntaps == 0 turns the decimator
+ * off and frees its state.  Every set call copies the taps, sizes the tails and zeroes them, even
+ * with unchanged parameters.  A change waits for the handle's decimator launches in flight (the
+ * rule of set_channel_fine_tune). */
+int sddc_ddc_set_channel_decimator(sddc_ddc_t *h, const float *taps, int ntaps, int factor, int nch);
+/* zero every channel's tail: the next call starts a new stream (SDDC_ERR_STATE: no decimator set) */
+int sddc_ddc_channel_decimator_reset(sddc_ddc_t *h);
+/* nsamp / factor; 0 if the factor is outside 2..64 or does not divide nsamp */
+size_t sddc_ddc_channel_decimate_samples(int factor, size_t nsamp);
+/* GPU handles; enqueued on hip_stream, returns after launch.  SDDC_ERR_STATE: no decimator set,
+ * another nch than the set one, a CPU handle.  SDDC_ERR_ARG: nsamp == 0 or no multiple of the
+ * factor, a bad stride or alignment, a null buffer.  A failed call changes no state.  The calls of
+ * one handle share the tails: they run one after the other in call order, whatever their streams
+ * (a call waits for the earlier calls' launches, as the spectrum calls do for their shared rows). */
+int sddc_ddc_channel_decimate_device(sddc_ddc_t *h, const void *d_iq, int nch, size_t nsamp, size_t in_stride,
+                                     float *d_out, size_t out_stride, void *hip_stream);
+/* Host buffers, the same layouts.  GPU handle: copy in, kernel, copy back, synchronous, in device
+ * buffers of its own; it advances the same device tails as the device call.  CPU handle: the AVX2
+ * backend, the same definition and bound (another fixed order of the sum). */
+int sddc_ddc_channel_decimate_host(sddc_ddc_t *h, const void *iq, int nch, size_t nsamp, size_t in_stride,
+                                   float *out, size_t out_stride);
 
 /* ---- ingest ---------------------------------------
  * Pin a caller-owned host region (hipHostRegister) so the host path DMAs blocks
