@@ -11,9 +11,12 @@ from .r2iq import (FFTN, SPECTRUM_BINS, WINDOW_BLACKMAN_HARRIS, WINDOW_HANN, WIN
 from .r2iq import CHANNEL_SPECTRUM_SIZES, window  # noqa: F401
 from .r2iq import (CHANNEL_DECIMATE_TILE, DECIM_MAX_FACTOR, DECIM_MAX_TAPS,  # noqa: F401
                    channel_decimate_samples)
+from .r2iq import (CHANNEL_RESAMPLE_MAX_DOWN, CHANNEL_RESAMPLE_MAX_PHASE_TAPS,  # noqa: F401
+                   CHANNEL_RESAMPLE_MAX_TAPS, CHANNEL_RESAMPLE_MAX_UP, resample_count)
 
 __all__ = ["R2iq", "DDCError", "DEVICE_CPU", "BACKEND_CPU", "BACKEND_HIP", "build", "load", "kaiser", "filter_taps", "filter_response",
            "channel_tuning", "device_count", "output_samples", "HALF_FFT", "BLOCK", "FRAMES", "NDEC", "OUT_BLOCK",
            "BBRF103_GAINFACTOR", "spectrum_window", "psd_to_dbfs", "FFTN", "SPECTRUM_BINS", "WINDOW_RECT", "WINDOW_HANN",
            "WINDOW_BLACKMAN_HARRIS", "window", "CHANNEL_SPECTRUM_SIZES", "channel_decimate_samples", "CHANNEL_DECIMATE_TILE",
-           "DECIM_MAX_TAPS", "DECIM_MAX_FACTOR"]
+           "DECIM_MAX_TAPS", "DECIM_MAX_FACTOR", "resample_count", "CHANNEL_RESAMPLE_MAX_UP", "CHANNEL_RESAMPLE_MAX_DOWN",
+           "CHANNEL_RESAMPLE_MAX_TAPS", "CHANNEL_RESAMPLE_MAX_PHASE_TAPS"]

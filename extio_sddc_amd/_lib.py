@@ -66,6 +66,12 @@ SIGNATURES = {
     "sddc_ddc_channel_decimate_samples": (_SZ, [_I, _SZ]),
     "sddc_ddc_channel_decimate_device": (_I, [_P, _P, _I, _SZ, _SZ, _P, _SZ, _P]),
     "sddc_ddc_channel_decimate_host": (_I, [_P, _P, _I, _SZ, _SZ, _P, _SZ]),
+    "sddc_ddc_set_channel_resampler": (_I, [_P, _P, _I, _I, _I, _I]),
+    "sddc_ddc_channel_resampler_reset": (_I, [_P]),
+    "sddc_ddc_resample_count": (_SZ, [_I, _I, ctypes.c_uint64, _SZ]),
+    "sddc_ddc_channel_resample_samples": (_SZ, [_P, _SZ]),
+    "sddc_ddc_channel_resample_device": (_I, [_P, _P, _I, _SZ, _SZ, _P, _SZ, _P, _P]),
+    "sddc_ddc_channel_resample_host": (_I, [_P, _P, _I, _SZ, _SZ, _P, _SZ, _P]),
     "sddc_ddc_register_host": (_I, [_P, _P, _SZ]),
     "sddc_ddc_unregister_host": (_I, [_P, _P]),
     # include/sddc_fft.h

@@ -382,5 +382,78 @@ void R2iq::channel_decimate(const void *iq, bool cs16, float inv_s, int nch, siz
     }
 }
 
+// The channel resampler (sddc_ddc_channel_resample_host on a CPU handle).  Per channel the stream
+// [tail | the call's samples] is split into I and Q rows; output k of the call has e + k M = s L + p
+// and is the dot product of phase p's reversed taps r_p[i] = h[p + (K - 1 - i) L] with the K values
+// from sample s - (K - 1) on: eight lane sums of explicit FMAs over i = 8 n + lane, added in a fixed
+// tree, then the last K mod 8 one by one.  The order depends on (p, i, K) alone, so any cut of a
+// stream into calls, at any position, gives the same bits.
+void R2iq::channel_resample(const void *iq, bool cs16, float inv_s, int nch, size_t nsamp, size_t in_stride,
+                            const float *taps, int ntaps, int L, int M, int e, size_t nout, float *tail, float *out,
+                            size_t out_stride)
+{
+    const int K = (ntaps + L - 1) / L;
+    const size_t H = (size_t)K - 1;
+    std::vector<float> g((size_t)L * (size_t)K), xr(H + nsamp), xi(H + nsamp);
+    for (int p = 0; p < L; p++)
+        for (int i = 0; i < K; i++) {
+            const int k = p + (K - 1 - i) * L;
+            g[(size_t)p * (size_t)K + (size_t)i] = k < ntaps ? taps[k] : 0.f;
+        }
+    for (int c = 0; c < nch; c++) {
+        float *tl = tail + (size_t)c * H * 2;
+        for (size_t k = 0; k < H; k++) {
+            xr[k] = tl[2 * k];
+            xi[k] = tl[2 * k + 1];
+        }
+        if (cs16) {
+            const int16_t *x = static_cast<const int16_t *>(iq) + (size_t)c * in_stride;
+            for (size_t i = 0; i < nsamp; i++) {
+                xr[H + i] = (float)x[2 * i] * inv_s;
+                xi[H + i] = (float)x[2 * i + 1] * inv_s;
+            }
+        } else {
+            const float *x = static_cast<const float *>(iq) + (size_t)c * in_stride;
+            for (size_t i = 0; i < nsamp; i++) {
+                xr[H + i] = x[2 * i];
+                xi[H + i] = x[2 * i + 1];
+            }
+        }
+        float *y = out + (size_t)c * out_stride;
+        uint64_t s = (uint64_t)e / (uint64_t)L;   // output k's sample and phase, stepped by M / L
+        int p = e % L;
+        const uint64_t ds = (uint64_t)(M / L);
+        const int dp = M % L;
+        for (size_t m = 0; m < nout; m++) {
+            // row index H + s - (K - 1) = s
+            const float *pr = xr.data() + s, *pi = xi.data() + s, *gp = g.data() + (size_t)p * (size_t)K;
+            __m256 ar = _mm256_setzero_ps(), ai = _mm256_setzero_ps();
+            int k = 0;
+            for (; k + 8 <= K; k += 8) {
+                const __m256 gv = _mm256_loadu_ps(gp + k);
+                ar = _mm256_fmadd_ps(gv, _mm256_loadu_ps(pr + k), ar);
+                ai = _mm256_fmadd_ps(gv, _mm256_loadu_ps(pi + k), ai);
+            }
+            float sr = hsum8(ar), si = hsum8(ai);
+            for (; k < K; k++) {
+                sr = std::fmaf(gp[k], pr[k], sr);
+                si = std::fmaf(gp[k], pi[k], si);
+            }
+            y[2 * m] = sr;
+            y[2 * m + 1] = si;
+            s += ds;
+            p += dp;
+            if (p >= L) {
+                p -= L;
+                s++;
+            }
+        }
+        for (size_t k = 0; k < H; k++) {   // the last H values of [tail | samples]
+            tl[2 * k] = xr[nsamp + k];
+            tl[2 * k + 1] = xi[nsamp + k];
+        }
+    }
+}
+
 }  // namespace cpu
 }  // namespace sddc

@@ -74,6 +74,14 @@ public:
     // channel's last sample values before the call, replaced by those after it.  Stateless otherwise.
     static void channel_decimate(const void *iq, bool cs16, float inv_s, int nch, size_t nsamp, size_t in_stride,
                                  const float *taps, int ntaps, int R, float *tail, float *out, size_t out_stride);
+    // The channel resampler (sddc_ddc.h, sddc_ddc_channel_resample_host): output k of the call has
+    // e + k M = s L + p and is sum_{j < K} taps[p + j L] x_c[s - j], K = ceil(ntaps / L), s counted from
+    // the call's first sample; e (0 <= e < M) is the call's reduced stream position and nout its
+    // outputs per channel (every s < nsamp).  Streams, formats, strides and tail ([nch][K - 1][2]
+    // floats) as for channel_decimate.  Stateless otherwise.
+    static void channel_resample(const void *iq, bool cs16, float inv_s, int nch, size_t nsamp, size_t in_stride,
+                                 const float *taps, int ntaps, int L, int M, int e, size_t nout, float *tail, float *out,
+                                 size_t out_stride);
 
 private:
     struct Buf;

@@ -218,6 +218,37 @@ hipError_t launch_channel_decimate(const KernelTables &t, const void *d_iq, int 
                                    const float2 *d_tail_in, float2 *d_tail_out, float *d_out, size_t out_stride,
                                    int max_wgs, int device, hipStream_t s);
 
+// Channel resampler (ddc_channel_resample.hip, sddc_ddc_channel_resample_device): the rational L / M
+// polyphase FIR y_c[m] = sum_{j < K} h[p + jL] x_c[s - j], m M = s L + p, K = ceil(ntaps / L), on nch
+// streams laid out as for the decimator; any nsamp >= 1.  e = the call's position (0 <= e < M: the
+// first output's m M minus the first sample's i L), nout = the call's outputs per channel
+// (= ceil((nsamp L - e) / M), checked), written as float2 at d_out + c * out_stride floats.
+// d_taps: [L][K] floats in the kernel's order (channel_resample_order_taps: g[p][j] = h[p + jL],
+// zero-padded).  d_tail_in / d_tail_out: [nch][K - 1] float2 as for the decimator (both may be null
+// when K == 1).  One work item per (channel, tile of ta values of a = ta L outputs); a call without
+// an output still moves the tails.  max_wgs > 0 caps the grid (tests).  The caller has checked the
+// strides.
+constexpr int kChResLds = 8128;        // float2 slots of LDS per tile (+ 64 of slack: 64 KiB, 2 workgroups per CU)
+constexpr int kChResMaxA = 512;        // values of a per tile at most (16 half-wave units per phase)
+constexpr int kChResPitchPad = 15;     // the pitch search's range above the columns needed
+constexpr int kChResMaxTaps = 4096;    // SDDC_DDC_RESAMPLE_MAX_TAPS
+constexpr int kChResMaxUp = 32;        // SDDC_DDC_RESAMPLE_MAX_UP
+constexpr int kChResMaxDown = 256;     // SDDC_DDC_RESAMPLE_MAX_DOWN
+constexpr int kChResMaxK = 1024;       // SDDC_DDC_RESAMPLE_MAX_PHASE_TAPS
+static_assert(kChResLds / kChResMaxDown - ((kChResMaxK - 2 + kChResMaxDown) / kChResMaxDown + 1) - 1 >= 1,
+              "a tile of both maxima holds an output");
+// The tile of (L, M, ntaps, format): K, the values of a per tile (ta L outputs), the polyphase rows'
+// pitch and the modelled extra LDS cycles of the stage's stores per wave.
+struct ChResLayout {
+    int K = 0, ta = 0, pitch = 0, store_conflicts = 0;
+};
+ChResLayout channel_resample_layout(int L, int M, int ntaps, int cs16);
+void channel_resample_order_taps(const float *h, int ntaps, int L, float *g /* [L][ceil(ntaps / L)] */);
+hipError_t launch_channel_resample(const KernelTables &t, const void *d_iq, int cs16, float cs16_scale, int nch,
+                                   size_t nsamp, size_t in_stride, const float *d_taps, int ntaps, int L, int M,
+                                   int e, size_t nout, const float2 *d_tail_in, float2 *d_tail_out, float *d_out,
+                                   size_t out_stride, int max_wgs, int device, hipStream_t s);
+
 // batched FFTs (fft_batch.hip, include/sddc_fft.h); fft_prepare fills the device's twiddle
 // table once (synchronises s the first time)
 hipError_t fft_prepare(hipStream_t s);

@@ -317,6 +317,22 @@ struct sddc_ddc {
     Readers chdec_readers;
     int chdec_max_wgs = 0;                 // SDDC_DDC_PARAM_CHDEC_MAX_WGS
 
+    // channel resampler (sddc_ddc_channel_resample_*): as the decimator's state, with K - 1 =
+    // ceil(ntaps / up) - 1 kept values per channel, and the stream position reduced to chres_e =
+    // m0 down - N up (0 <= chres_e < down) for N samples consumed and m0 = ceil(N up / down)
+    // outputs produced: all a call needs, and no product overflows at any stream length.
+    std::vector<float> chres_taps;
+    int chres_L = 0, chres_M = 0, chres_K = 0, chres_nch = 0, chres_e = 0;
+    float *d_chres_taps = nullptr;         // [up][K] in the kernel's order
+    float2 *d_chres_tail[2] = {};          // [chres_nch][K - 1] each
+    int chres_cur = 0;
+    std::vector<float> chres_tail_h;       // CPU handle: [chres_nch][K - 1][2]
+    void *d_chres_in = nullptr;            // channel_resample_host
+    float *d_chres_out = nullptr;
+    size_t chres_in_cap = 0, chres_out_cap = 0;   // bytes, floats
+    Readers chres_readers;
+    int chres_max_wgs = 0;                 // SDDC_DDC_PARAM_CHRES_MAX_WGS
+
     // CPU handle (device SDDC_DDC_DEVICE_CPU): the AVX2 backend; no HIP object above exists
     std::unique_ptr<sddc::cpu::R2iq> cpu;
 
@@ -533,6 +549,7 @@ int sddc_ddc_destroy(sddc_ddc_t *h)
         (void)h->sp_readers.sync();
         (void)h->chsp_readers.sync();
         (void)h->chdec_readers.sync();
+        (void)h->chres_readers.sync();
         if (h->d_tables) (void)hipFree(h->d_tables);
         for (auto &sl : h->hs) {
             if (sl.d_in) (void)hipFree(sl.d_in);
@@ -570,6 +587,12 @@ int sddc_ddc_destroy(sddc_ddc_t *h)
         if (h->d_chdec_in) (void)hipFree(h->d_chdec_in);
         if (h->d_chdec_out) (void)hipFree(h->d_chdec_out);
         h->chdec_readers.clear();
+        if (h->d_chres_taps) (void)hipFree(h->d_chres_taps);
+        for (float2 *p : h->d_chres_tail)
+            if (p) (void)hipFree(p);
+        if (h->d_chres_in) (void)hipFree(h->d_chres_in);
+        if (h->d_chres_out) (void)hipFree(h->d_chres_out);
+        h->chres_readers.clear();
         if (h->fsa.h_ring) (void)hipHostFree(h->fsa.h_ring);   // its writers were waited for above
         h->readers.clear();
         h->ch_readers.clear();
@@ -1087,6 +1110,10 @@ int sddc_ddc_internal_set_param(sddc_ddc_t *h, int param, int value)
     case SDDC_DDC_PARAM_CHDEC_MAX_WGS:
         if (value < 0) return fail(SDDC_ERR_ARG, "channel decimator workgroup cap %d is negative", value);
         h->chdec_max_wgs = value;
+        return SDDC_OK;
+    case SDDC_DDC_PARAM_CHRES_MAX_WGS:
+        if (value < 0) return fail(SDDC_ERR_ARG, "channel resampler workgroup cap %d is negative", value);
+        h->chres_max_wgs = value;
         return SDDC_OK;
     default:
         return fail(SDDC_ERR_ARG, "unknown parameter %d", param);
@@ -1855,6 +1882,318 @@ int sddc_ddc_channel_decimate_host(sddc_ddc_t *h, const void *iq, int nch, size_
                                      2 * nout * sizeof(float), (size_t)nch, hipMemcpyDeviceToHost, h->stream));
     }
     HIP_TRY(hipStreamSynchronize(h->stream));   // also after a failed launch: the caller's input is free again
+    return rc;
+}
+
+/* ---- channel resampler: a streaming rational L/M polyphase FIR on the DDC's IQ output ------ */
+static_assert(SDDC_DDC_RESAMPLE_MAX_TAPS == sddc::kChResMaxTaps && SDDC_DDC_RESAMPLE_MAX_UP == sddc::kChResMaxUp &&
+                  SDDC_DDC_RESAMPLE_MAX_DOWN == sddc::kChResMaxDown && SDDC_DDC_RESAMPLE_MAX_PHASE_TAPS == sddc::kChResMaxK,
+              "the kernel's limits are the ABI's");
+
+static int chres_gcd(int a, int b)
+{
+    while (b) {
+        const int t = a % b;
+        a = b;
+        b = t;
+    }
+    return a;
+}
+
+// the factors of the ABI: ranges, coprime, not the identity
+static bool chres_factors_ok(int up, int down)
+{
+    return up >= 1 && up <= SDDC_DDC_RESAMPLE_MAX_UP && down >= 1 && down <= SDDC_DDC_RESAMPLE_MAX_DOWN &&
+           chres_gcd(up, down) == 1 && !(up == 1 && down == 1);
+}
+
+// The reduced position of N samples consumed: e = ceil(N up / down) down - N up = (-N up) mod down.
+static int chres_position(int up, int down, uint64_t pos)
+{
+    const int r = (int)((pos % (uint64_t)down) * (uint64_t)up % (uint64_t)down);
+    return r ? down - r : 0;
+}
+
+// Outputs of nsamp <= 2^40 samples at the reduced position e: the k >= 0 with e + k down < nsamp up.
+static size_t chres_count(int up, int down, int e, size_t nsamp)
+{
+    const uint64_t span = (uint64_t)nsamp * (uint64_t)up;
+    return span > (uint64_t)e ? (size_t)((span - (uint64_t)e + (uint64_t)down - 1) / (uint64_t)down) : 0;
+}
+
+// the position after that call: e + nout down - nsamp up
+static int chres_advance(int up, int down, int e, size_t nsamp, size_t nout)
+{
+    return (int)((int64_t)e + (int64_t)nout * down - (int64_t)nsamp * up);
+}
+
+// off: no taps, no tails (the caller holds h->mu and has waited for the launches in flight)
+static void chres_clear(sddc_ddc_t *h)
+{
+    h->chres_taps.clear();
+    h->chres_L = h->chres_M = h->chres_K = h->chres_nch = h->chres_e = 0;
+    h->chres_tail_h.clear();
+    for (float2 *&p : h->d_chres_tail) {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+    }
+    h->chres_cur = 0;
+}
+
+/* internal (sddc_ddc_internal.h): the kernel's tile of (up, down, ntaps, format) */
+int sddc_ddc_internal_chres_layout(int up, int down, int ntaps, int cs16, int *tile_outputs, int *pitch,
+                                   int *store_conflicts)
+{
+    if (!chres_factors_ok(up, down) || ntaps < 1 || ntaps > SDDC_DDC_RESAMPLE_MAX_TAPS ||
+        (ntaps + up - 1) / up > SDDC_DDC_RESAMPLE_MAX_PHASE_TAPS || !tile_outputs || !pitch || !store_conflicts)
+        return fail(SDDC_ERR_ARG, "chres layout: up %d, down %d, ntaps %d or a null pointer", up, down, ntaps);
+    const sddc::ChResLayout g = sddc::channel_resample_layout(up, down, ntaps, cs16);
+    *tile_outputs = g.ta * up;
+    *pitch = g.pitch;
+    *store_conflicts = g.store_conflicts;
+    return SDDC_OK;
+}
+
+/* internal: the stream position, the tails left as they are */
+int sddc_ddc_internal_chres_set_position(sddc_ddc_t *h, uint64_t pos)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->chres_taps.empty()) return fail(SDDC_ERR_STATE, "chres set position: no resampler set");
+    h->chres_e = chres_position(h->chres_L, h->chres_M, pos);   // host state: a launch in flight has its own copy
+    return SDDC_OK;
+}
+
+int sddc_ddc_set_channel_resampler(sddc_ddc_t *h, const float *taps, int ntaps, int up, int down, int nch)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    const bool off = !taps || ntaps == 0;
+    int K = 0;
+    if (!off) {
+        if (ntaps < 1 || ntaps > SDDC_DDC_RESAMPLE_MAX_TAPS)
+            return fail(SDDC_ERR_ARG, "channel resampler: ntaps %d outside 1..%d", ntaps, SDDC_DDC_RESAMPLE_MAX_TAPS);
+        if (!chres_factors_ok(up, down))
+            return fail(SDDC_ERR_ARG, "channel resampler: up %d (1..%d) and down %d (1..%d) must be coprime and not both 1",
+                        up, SDDC_DDC_RESAMPLE_MAX_UP, down, SDDC_DDC_RESAMPLE_MAX_DOWN);
+        K = (ntaps + up - 1) / up;
+        if (K > SDDC_DDC_RESAMPLE_MAX_PHASE_TAPS)
+            return fail(SDDC_ERR_ARG, "channel resampler: ceil(ntaps / up) = %d is above %d", K,
+                        SDDC_DDC_RESAMPLE_MAX_PHASE_TAPS);
+        if (nch < 1 || nch > SDDC_DDC_MAX_CHANNELS)
+            return fail(SDDC_ERR_ARG, "channel resampler: nch %d outside 1..%d", nch, SDDC_DDC_MAX_CHANNELS);
+        for (int j = 0; j < ntaps; j++)
+            if (!std::isfinite(taps[j])) return fail(SDDC_ERR_ARG, "channel resampler: tap %d is not finite", j);
+    }
+    std::lock_guard<std::mutex> lk(h->mu);
+    const size_t tail = off ? 0 : (size_t)nch * (size_t)(K - 1);   // complex values
+    if (h->cpu) {
+        chres_clear(h);
+        if (off) return SDDC_OK;
+        try {
+            h->chres_tail_h.assign(2 * tail, 0.f);
+            h->chres_taps.assign(taps, taps + ntaps);
+        } catch (const std::exception &ex) {
+            chres_clear(h);
+            return fail(SDDC_ERR_NOMEM, "channel resampler: %s", ex.what());
+        }
+        h->chres_L = up;
+        h->chres_M = down;
+        h->chres_K = K;
+        h->chres_nch = nch;
+        return SDDC_OK;
+    }
+    DeviceGuard g(h->device);
+    HIP_TRY(g.err);
+    HIP_TRY(h->chres_readers.sync());   // earlier launches, on any stream, may still use the taps and the tails
+    chres_clear(h);                     // a failed upload leaves the resampler off
+    if (off) return SDDC_OK;
+    constexpr size_t kOrdered = SDDC_DDC_RESAMPLE_MAX_TAPS + SDDC_DDC_RESAMPLE_MAX_UP;   // up K < ntaps + up
+    if (!h->d_chres_taps) HIP_TRY(hipMalloc(&h->d_chres_taps, kOrdered * sizeof(float)));
+    try {   // the device copy is in the kernel's order
+        std::vector<float> ordered((size_t)up * (size_t)K);
+        sddc::channel_resample_order_taps(taps, ntaps, up, ordered.data());
+        HIP_TRY(hipMemcpy(h->d_chres_taps, ordered.data(), ordered.size() * sizeof(float), hipMemcpyHostToDevice));
+    } catch (const std::exception &ex) {
+        return fail(SDDC_ERR_NOMEM, "channel resampler: %s", ex.what());
+    }
+    if (tail) {
+        for (float2 *&p : h->d_chres_tail) {
+            if (hipMalloc(&p, tail * sizeof(float2)) != hipSuccess) {
+                (void)hipGetLastError();
+                p = nullptr;
+                chres_clear(h);
+                return fail(SDDC_ERR_NOMEM, "channel resampler: no device memory for %zu tail values", tail);
+            }
+        }
+        // zeroed on the handle's stream and waited for: the first launch may be on any stream
+        hipError_t e = hipMemsetAsync(h->d_chres_tail[0], 0, tail * sizeof(float2), h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) {
+            chres_clear(h);
+            HIP_TRY(e);
+        }
+    }
+    h->chres_taps.assign(taps, taps + ntaps);
+    h->chres_L = up;
+    h->chres_M = down;
+    h->chres_K = K;
+    h->chres_nch = nch;
+    return SDDC_OK;
+}
+
+int sddc_ddc_channel_resampler_reset(sddc_ddc_t *h)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->chres_taps.empty()) return fail(SDDC_ERR_STATE, "channel resampler reset: no resampler set");
+    if (h->cpu) {
+        std::fill(h->chres_tail_h.begin(), h->chres_tail_h.end(), 0.f);
+        h->chres_e = 0;
+        return SDDC_OK;
+    }
+    const size_t tail = (size_t)h->chres_nch * (size_t)(h->chres_K - 1);
+    if (tail) {
+        DeviceGuard g(h->device);
+        HIP_TRY(g.err);
+        HIP_TRY(h->chres_readers.sync());   // earlier launches, on any stream, may still use the tails
+        HIP_TRY(hipMemsetAsync(h->d_chres_tail[h->chres_cur], 0, tail * sizeof(float2), h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));   // the next launch may be on any stream
+    }
+    h->chres_e = 0;
+    return SDDC_OK;
+}
+
+size_t sddc_ddc_resample_count(int up, int down, uint64_t pos, size_t nsamp)
+{
+    if (!chres_factors_ok(up, down) || nsamp > ((size_t)1 << 40)) return 0;
+    return chres_count(up, down, chres_position(up, down, pos), nsamp);
+}
+
+size_t sddc_ddc_channel_resample_samples(sddc_ddc_t *h, size_t nsamp)
+{
+    if (!h) return 0;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->chres_taps.empty() || nsamp > ((size_t)1 << 40)) return 0;
+    return chres_count(h->chres_L, h->chres_M, h->chres_e, nsamp);
+}
+
+// the checks both calls share (under h->mu: the format, the resampler and the position are read here)
+static int check_chres_args(const sddc_ddc_t *h, const void *iq, int nch, size_t nsamp, size_t in_stride,
+                            const float *out, size_t out_stride, size_t *nout)
+{
+    if (h->chres_taps.empty()) return fail(SDDC_ERR_STATE, "channel resample: no resampler set");
+    if (nch != h->chres_nch)
+        return fail(SDDC_ERR_STATE, "channel resample: the resampler is set for %d channels, the call has %d",
+                    h->chres_nch, nch);
+    if (nsamp == 0 || nsamp > ((size_t)1 << 40))
+        return fail(SDDC_ERR_ARG, "nsamp must be in 1..2^40 (got %zu)", nsamp);
+    const size_t n = chres_count(h->chres_L, h->chres_M, h->chres_e, nsamp);
+    if (nch > 1 && (in_stride < 2 * nsamp || (in_stride & 1) != 0))
+        return fail(SDDC_ERR_ARG, "in_stride must be even and >= 2 nsamp (got %zu, nsamp %zu)", in_stride, nsamp);
+    if (nch > 1 && (out_stride < 2 * n || (out_stride & 1) != 0))
+        return fail(SDDC_ERR_ARG, "out_stride must be even and >= 2 nout (got %zu, need %zu)", out_stride, 2 * n);
+    if (!iq || !out) return fail(SDDC_ERR_ARG, "null buffer");
+    const uintptr_t sample = h->out_fmt == SDDC_DDC_FMT_CS16 ? 4 : 8;
+    if (((uintptr_t)iq & (sample - 1)) != 0) return fail(SDDC_ERR_ARG, "iq must be %d-byte aligned", (int)sample);
+    if (((uintptr_t)out & 7) != 0) return fail(SDDC_ERR_ARG, "the output must be 8-byte aligned");
+    *nout = n;
+    return SDDC_OK;
+}
+
+// One launch on s: it reads the current tails and writes the other buffer, so it runs after every
+// earlier launch of the handle, whatever its stream; the buffers swap and the position advances
+// once it is enqueued.
+static int chres_launch(sddc_ddc_t *h, const void *d_iq, int nch, size_t nsamp, size_t in_stride, float *d_out,
+                        size_t out_stride, size_t nout, hipStream_t s)
+{
+    HIP_TRY(h->chres_readers.order_before(s));
+    const int cur = h->chres_cur;
+    const hipError_t e = sddc::launch_channel_resample(
+        h->tables, d_iq, h->out_fmt == SDDC_DDC_FMT_CS16, h->cs16_scale, nch, nsamp, in_stride, h->d_chres_taps,
+        (int)h->chres_taps.size(), h->chres_L, h->chres_M, h->chres_e, nout, h->d_chres_tail[cur],
+        h->d_chres_tail[cur ^ 1], d_out, out_stride, h->chres_max_wgs, h->device, s);
+    const hipError_t er = h->chres_readers.record(s);   // whatever was enqueued stays ordered
+    HIP_TRY(e);
+    if (h->chres_K > 1) h->chres_cur = cur ^ 1;
+    h->chres_e = chres_advance(h->chres_L, h->chres_M, h->chres_e, nsamp, nout);
+    HIP_TRY(er);
+    return SDDC_OK;
+}
+
+int sddc_ddc_channel_resample_device(sddc_ddc_t *h, const void *d_iq, int nch, size_t nsamp, size_t in_stride,
+                                     float *d_out, size_t out_stride, size_t *nout, void *hip_stream)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(h->mu);   // the call reads the format and the resampler: one consistent set
+    if (h->cpu) return fail(SDDC_ERR_STATE, "channel_resample_device: a CPU handle has no device path");
+    size_t n = 0;
+    if (int rc = check_chres_args(h, d_iq, nch, nsamp, in_stride, d_out, out_stride, &n)) return rc;
+    DeviceGuard g(h->device);
+    HIP_TRY(g.err);
+    if (int rc = chres_launch(h, d_iq, nch, nsamp, in_stride, d_out, out_stride, n, (hipStream_t)hip_stream)) return rc;
+    if (nout) *nout = n;
+    return SDDC_OK;
+}
+
+int sddc_ddc_channel_resample_host(sddc_ddc_t *h, const void *iq, int nch, size_t nsamp, size_t in_stride, float *out,
+                                   size_t out_stride, size_t *nout_p)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    size_t nout = 0;
+    if (int rc = check_chres_args(h, iq, nch, nsamp, in_stride, out, out_stride, &nout)) return rc;
+    const bool cs16 = h->out_fmt == SDDC_DDC_FMT_CS16;
+    if (h->cpu) {
+        try {
+            sddc::cpu::R2iq::channel_resample(iq, cs16, (float)(1.0 / (double)h->cs16_scale), nch, nsamp,
+                                              nch > 1 ? in_stride : 0, h->chres_taps.data(), (int)h->chres_taps.size(),
+                                              h->chres_L, h->chres_M, h->chres_e, nout, h->chres_tail_h.data(), out,
+                                              nch > 1 ? out_stride : 0);
+        } catch (const std::exception &ex) {   // thrown before any output or tail is written
+            return fail(SDDC_ERR_NOMEM, "cpu backend: %s", ex.what());
+        }
+        h->chres_e = chres_advance(h->chres_L, h->chres_M, h->chres_e, nsamp, nout);
+        if (nout_p) *nout_p = nout;
+        return SDDC_OK;
+    }
+    DeviceGuard g(h->device);
+    HIP_TRY(g.err);
+    // the spans that hold every channel's samples and outputs (one float2 at least: a call without an output)
+    const size_t in_bytes = ((size_t)(nch - 1) * (nch > 1 ? in_stride : 0) + 2 * nsamp) * (cs16 ? 2 : 4);
+    const size_t out_floats = (size_t)(nch - 1) * (nch > 1 ? out_stride : 0) + 2 * nout;
+    const size_t out_alloc = out_floats ? out_floats : 2;
+    // the earlier host calls were synchronous: nothing reads the old buffers
+    if (in_bytes > h->chres_in_cap) {
+        if (h->d_chres_in) (void)hipFree(h->d_chres_in);
+        h->d_chres_in = nullptr;
+        h->chres_in_cap = 0;
+        if (hipMalloc(&h->d_chres_in, in_bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(SDDC_ERR_NOMEM, "channel_resample_host: no device memory for %zu input bytes", in_bytes);
+        }
+        h->chres_in_cap = in_bytes;
+    }
+    if (out_alloc > h->chres_out_cap) {
+        if (h->d_chres_out) (void)hipFree(h->d_chres_out);
+        h->d_chres_out = nullptr;
+        h->chres_out_cap = 0;
+        if (hipMalloc(&h->d_chres_out, out_alloc * sizeof(float)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(SDDC_ERR_NOMEM, "channel_resample_host: no device memory for %zu output floats", out_alloc);
+        }
+        h->chres_out_cap = out_alloc;
+    }
+    HIP_TRY(hipMemcpyAsync(h->d_chres_in, iq, in_bytes, hipMemcpyHostToDevice, h->stream));
+    const int rc = chres_launch(h, h->d_chres_in, nch, nsamp, in_stride, h->d_chres_out, out_stride, nout, h->stream);
+    if (rc == SDDC_OK && nout) {   // the streams alone: the caller's memory between them stays as it is
+        if (nch == 1 || out_stride == 2 * nout)
+            HIP_TRY(hipMemcpyAsync(out, h->d_chres_out, out_floats * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        else
+            HIP_TRY(hipMemcpy2DAsync(out, out_stride * sizeof(float), h->d_chres_out, out_stride * sizeof(float),
+                                     2 * nout * sizeof(float), (size_t)nch, hipMemcpyDeviceToHost, h->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(h->stream));   // also after a failed launch: the caller's input is free again
+    if (rc == SDDC_OK && nout_p) *nout_p = nout;
     return rc;
 }
 

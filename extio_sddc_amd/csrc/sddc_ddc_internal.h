@@ -59,6 +59,10 @@ extern "C" {
  * workgroups; 0 (default): one workgroup per item, or full residency with a loop.  The grid changes
  * no output bit (tests). */
 #define SDDC_DDC_PARAM_CHDEC_MAX_WGS 13
+/* SDDC_DDC_PARAM_CHRES_MAX_WGS = n > 0: the channel resampler kernel's grid is at most n workgroups,
+ * as param 13 for the decimator; 0 (default): one workgroup per item, or full residency with a
+ * loop.  The grid changes no output bit (tests). */
+#define SDDC_DDC_PARAM_CHRES_MAX_WGS 14
 
 int sddc_ddc_internal_set_param(sddc_ddc_t *h, int param, int value);
 /* A given table of n relative shares (n = the d = 0 kernel's full-residency grid, 4 x CUs) used as
@@ -72,6 +76,15 @@ int sddc_ddc_internal_fs_split_state(sddc_ddc_t *h, long *info, int *counts, int
  * rows' pitch in float2 slots, and the modelled extra LDS cycles of the stage's stores per wave
  * (tools/channel_decimate_banks.py; no handle, no device).  SDDC_ERR_ARG outside the ABI's ranges. */
 int sddc_ddc_internal_chdec_layout(int factor, int ntaps, int cs16, int *tile, int *pitch, int *store_conflicts);
+/* The channel resampler kernel's tile of (up, down, ntaps, format): outputs per tile (up x the
+ * tile's values of a), the polyphase rows' pitch in float2 slots, and the modelled extra LDS cycles
+ * of the stage's stores per wave (tools/channel_resample_banks.py; no handle, no device).
+ * SDDC_ERR_ARG outside the ABI's ranges. */
+int sddc_ddc_internal_chres_layout(int up, int down, int ntaps, int cs16, int *tile_outputs, int *pitch,
+                                   int *store_conflicts);
+/* Set the resampler's stream position to pos samples consumed (any value: it is kept reduced), the
+ * tails left as they are: tests start a stream far out.  SDDC_ERR_STATE: no resampler set. */
+int sddc_ddc_internal_chres_set_position(sddc_ddc_t *h, uint64_t pos);
 /* The controller alone (no handle, no device): tests/test_adaptive_split.py. */
 void *sddc_fs_split_create(int G, unsigned slot_weights);
 void sddc_fs_split_destroy(void *c);

@@ -116,6 +116,21 @@ def channel_decimate_samples(factor: int, nsamp: int) -> int:
     return int(_lib.load().sddc_ddc_channel_decimate_samples(int(factor), int(nsamp)))
 
 
+CHANNEL_RESAMPLE_MAX_UP = 32             # SDDC_DDC_RESAMPLE_MAX_UP
+CHANNEL_RESAMPLE_MAX_DOWN = 256          # SDDC_DDC_RESAMPLE_MAX_DOWN
+CHANNEL_RESAMPLE_MAX_TAPS = 4096         # SDDC_DDC_RESAMPLE_MAX_TAPS
+CHANNEL_RESAMPLE_MAX_PHASE_TAPS = 1024   # SDDC_DDC_RESAMPLE_MAX_PHASE_TAPS: ceil(ntaps / up)
+
+
+def resample_count(up: int, down: int, pos: int, nsamp: int) -> int:
+    """Outputs per channel of a channel_resample call of nsamp samples at stream position pos:
+    ceil((pos + nsamp) up / down) - ceil(pos up / down); 0 on factors outside 1..32 / 1..256, not
+    coprime or both 1 (sddc_ddc_resample_count)."""
+    if nsamp < 0 or pos < 0:
+        return 0
+    return int(_lib.load().sddc_ddc_resample_count(int(up), int(down), int(pos) & (2 ** 64 - 1), int(nsamp)))
+
+
 def psd_to_dbfs(psd) -> np.ndarray:
     """R2iq.spectrum's output in dB relative to a full-scale real tone (amplitude 32768 reads
     32768^2 / 4 at its bin centre): 10 log10(4 psd / 32768^2); -inf where psd is 0."""
@@ -143,6 +158,7 @@ class R2iq:
         self._lsb = False
         self._fmt = FMT_CF32
         self._decim = None   # (ntaps, factor, nch) of setChannelDecimator
+        self._resamp = None  # (ntaps, up, down, nch) of setChannelResampler
 
     # -- lifecycle --------------------------------------------------------
     @property
@@ -462,6 +478,90 @@ class R2iq:
             raise DDCError(-1, f"d_out has {d_out.numel()} floats, need {need}")
         check(self._L.sddc_ddc_channel_decimate_device(self._h, d_iq.data_ptr(), nch, nsamp, in_stride,
                                                        d_out.data_ptr(), out_stride, _stream_handle(stream)))
+
+    # -- channel resampler ------------------------------------------------------
+    def setChannelResampler(self, taps, up: int = 0, down: int = 0, nch: int = 0) -> None:
+        """The streaming rational up / down polyphase FIR of channel_resample: real prototype taps
+        (1..4096, at the input rate x up; ceil(ntaps / up) <= 1024), coprime factors 1..32 and
+        1..256, and the channel count of the calls that follow.  There is no implied gain: for
+        unity passband gain give taps with DC gain `up` (e.g. up * kaiser(...)).  Every call zeroes
+        the kept stream tails and the position.  None or no taps turns the resampler off."""
+        if taps is None or len(taps) == 0:
+            check(self._L.sddc_ddc_set_channel_resampler(self._h, None, 0, 0, 0, 0))
+            self._resamp = None
+            return
+        t = np.ascontiguousarray(np.asarray(taps, np.float32).reshape(-1))
+        check(self._L.sddc_ddc_set_channel_resampler(self._h, t.ctypes.data, t.size, int(up), int(down), int(nch)))
+        self._resamp = (t.size, int(up), int(down), int(nch))
+
+    def resetChannelResampler(self) -> None:
+        """Zero every channel's tail and the stream position: the next call starts a new stream."""
+        check(self._L.sddc_ddc_channel_resampler_reset(self._h))
+
+    def channel_resample_samples(self, nsamp: int) -> int:
+        """Outputs per channel that the NEXT channel_resample call of nsamp samples produces (it
+        depends on the stream position; 0 is a legal count)."""
+        if self._resamp is None or nsamp < 0:
+            return 0
+        return int(self._L.sddc_ddc_channel_resample_samples(self._h, int(nsamp)))
+
+    def channel_resample(self, iq: np.ndarray) -> np.ndarray:
+        """The resampler on host arrays: iq is complex64 [nch, nsamp] (CF32) or int16 [nch, nsamp, 2]
+        (CS16), matching the handle's output format, any nsamp >= 1; a single stream may drop the
+        channel axis.  Returns complex64 [nch, nout] (nout may be 0) and keeps each channel's last
+        ceil(ntaps / up) - 1 samples and the position for the next call."""
+        if self._resamp is None:
+            raise DDCError(-4, "no channel resampler set")
+        iq = np.asarray(iq)
+        if self._fmt == FMT_CS16:
+            if iq.dtype != np.int16 or iq.ndim not in (2, 3) or iq.shape[-1] != 2:
+                raise DDCError(-1, "CS16 handle: iq must be int16 [nch, nsamp, 2]")
+            iq = np.ascontiguousarray(iq.reshape((1,) + iq.shape if iq.ndim == 2 else iq.shape))
+        else:
+            if iq.dtype != np.complex64 or iq.ndim not in (1, 2):
+                raise DDCError(-1, "CF32 handle: iq must be complex64 [nch, nsamp]")
+            iq = np.ascontiguousarray(iq.reshape(1, -1) if iq.ndim == 1 else iq)
+        nch, nsamp = iq.shape[0], iq.shape[1]
+        if nsamp < 1:
+            raise DDCError(-1, "nsamp must be >= 1")
+        nout = self.channel_resample_samples(nsamp)
+        out = np.empty((nch, max(nout, 1)), np.complex64)
+        got = ctypes.c_size_t(0)
+        check(self._L.sddc_ddc_channel_resample_host(self._h, iq.ctypes.data, nch, nsamp, 2 * nsamp, out.ctypes.data,
+                                                     2 * max(nout, 1), ctypes.addressof(got)))
+        return out[:, :got.value]
+
+    def channel_resample_device(self, d_iq, nch: int, nsamp: int, in_stride: int, d_out, out_stride: int,
+                                stream=None) -> int:
+        """The resampler on the buffer process_device / process_channels_device wrote: d_iq is a
+        float32 (CS16: int16) device tensor, channel c at c * in_stride components, nsamp complex
+        samples each; d_out float32, channel c's nout (I, Q) pairs at c * out_stride floats.  Returns
+        nout = channel_resample_samples(nsamp) at the call (possibly 0).  Enqueued on `stream` like
+        process_device; the calls of one handle run in call order."""
+        import torch
+        if self._resamp is None:
+            raise DDCError(-4, "no channel resampler set")
+        if not (d_iq.is_cuda and d_out.is_cuda):
+            raise DDCError(-1, "device path needs device tensors")
+        want = torch.int16 if self._fmt == FMT_CS16 else torch.float32
+        if d_iq.dtype != want or d_out.dtype != torch.float32:
+            raise DDCError(-1, f"d_iq must be {want} and d_out float32")
+        if not (d_iq.is_contiguous() and d_out.is_contiguous()):
+            raise DDCError(-1, "tensors must be contiguous")
+        if nch < 1 or nsamp < 1:
+            raise DDCError(-1, "nch and nsamp must be >= 1")
+        nout = self.channel_resample_samples(nsamp)
+        need = (nch - 1) * in_stride + 2 * nsamp
+        if d_iq.numel() < need:
+            raise DDCError(-1, f"d_iq has {d_iq.numel()} components, need {need}")
+        need = (nch - 1) * out_stride + 2 * nout
+        if d_out.numel() < need:
+            raise DDCError(-1, f"d_out has {d_out.numel()} floats, need {need}")
+        got = ctypes.c_size_t(0)
+        check(self._L.sddc_ddc_channel_resample_device(self._h, d_iq.data_ptr(), nch, nsamp, in_stride,
+                                                       d_out.data_ptr(), out_stride, ctypes.addressof(got),
+                                                       _stream_handle(stream)))
+        return int(got.value)
 
 
 def _check_device_buffers(d_in, nblk, d_out, out_floats, fmt=0):

@@ -51,7 +51,10 @@ extern "C" {
                                        channel_spectrum_device, channel_spectrum_host (new symbols only);
                                        still 3: + set_channel_decimator, channel_decimator_reset,
                                        channel_decimate_samples, channel_decimate_device,
-                                       channel_decimate_host (new symbols only) */
+                                       channel_decimate_host (new symbols only);
+                                       still 3: + set_channel_resampler, channel_resampler_reset,
+                                       resample_count, channel_resample_samples,
+                                       channel_resample_device, channel_resample_host (new symbols only) */
 
 #define SDDC_DDC_HALF_FFT   4096    /* halfFft               fft_mt_r2iq.h:18 */
 #define SDDC_DDC_FFTN       8192    /* FFTN_R_ADC            config.h:49 */
@@ -340,6 +343,72 @@ int sddc_ddc_channel_decimate_device(sddc_ddc_t *h, const void *d_iq, int nch, s
  * backend, the same definition and bound (another fixed order of the sum). */
 int sddc_ddc_channel_decimate_host(sddc_ddc_t *h, const void *iq, int nch, size_t nsamp, size_t in_stride,
                                    float *out, size_t out_stride);
+
+/* ---- channel resampler: a streaming rational L/M polyphase FIR per channel ------------------
+ * The DDC and the channel decimator produce fs_adc / 2^(d+1) / R; the rates demodulators want (48 k
+ * audio, 192 k or 250 k WFM, 2.048 M or 2.4 M, symbol-rate multiples) are rational multiples of
+ * those.  For channel c, the real prototype taps h[0..ntaps-1], the interpolation factor L (up) and
+ * the decimation factor M (down):
+ *   u_c[i*L] = x_c[i], u_c = 0 elsewhere;   v_c[n] = sum_k h[k] u_c[n - k];   y_c[m] = v_c[m*M]
+ * which, with m*M = s*L + p (0 <= p < L), K = ceil(ntaps / L) and h[k] = 0 for k >= ntaps, is
+ *   y_c[m] = sum_{j < K} h[p + j*L] * x_c[s - j],      x_c[i] = 0 for i < 0.
+ * There is NO implied gain: zero-stuffing divides the passband gain by L, so a caller who wants
+ * unity gain designs h with DC gain L.  Example, 1 MS/s -> 48 kS/s (6/125): the prototype runs at
+ * 6 MS/s; a pass band to 15 kHz = 0.0025 of that rate and a stop band from 48 - 15 = 33 kHz = 0.0055
+ * keep every alias out of the pass band (70 dB with 1536 taps):
+ *   sddc_ddc_kaiser(1536, 70.0f, 0.0025f, 0.0055f, taps);   for (i = 0; i < 1536; i++) taps[i] *= 6;
+ *   sddc_ddc_set_channel_resampler(h, taps, 1536, 6, 125, nch);
+ * Output m exists once sample s = floor(m*M/L) has been consumed: after N samples in total the
+ * stream has produced ceil(N*L/M) outputs, so a call of nsamp samples at position N0 produces
+ * ceil((N0+nsamp)*L/M) - ceil(N0*L/M) outputs per channel (sddc_ddc_resample_count).  That count
+ * may be 0 (M > L and a short call): such a call is legal, writes nothing and still advances the
+ * tails and the position.  nsamp is any value >= 1 (at most 2^40).
+ * State per handle: each channel's last K-1 sample values as float32 (on the device for a GPU
+ * handle, on the host for a CPU handle), and one stream position shared by all channels, kept on
+ * the host in reduced form (the phase depends on it modulo M only), so a stream of any length
+ * overflows nothing.
+ * Input and output: exactly as for the channel decimator (in_stride / out_stride in components /
+ * floats, even, >= 2*nsamp / 2*nout when nch > 1; the input is read in the handle's CURRENT output
+ * format, CS16 as (float)v * (float)(1.0 / (double)cs16_scale); the output is CF32, 8-byte
+ * aligned).  Nothing is written between the streams or outside them.
+ * A stored output depends only on its K sample values and its phase's taps, through the sequence
+ * a[j mod 4] = fma(h[p + j*L], x[s - j], a[j mod 4]), j = 0 .. K-1, y = (a0 + a1) + (a2 + a3) on the
+ * device (another fixed order on a CPU handle): it is bit-identical from run to run, on any
+ * stream, for any grid, for a channel alone or among others, for any cut of the same samples
+ * into calls and at any stream position.  Each component is within
+ * gamma * sum_j |h[p + j*L]| |x[s - j]|, gamma = n u / (1 - n u), n = K + 1, u = 2^-24, of the exact sum.
+ * The decimator and the resampler may both be set on one handle; their states are independent. */
+#define SDDC_DDC_RESAMPLE_MAX_UP         32
+#define SDDC_DDC_RESAMPLE_MAX_DOWN       256
+#define SDDC_DDC_RESAMPLE_MAX_TAPS       4096
+#define SDDC_DDC_RESAMPLE_MAX_PHASE_TAPS 1024   /* K = ceil(ntaps / up) */
+/* taps: host array of ntaps floats (1..4096, all finite), 1 <= up <= 32, 1 <= down <= 256,
+ * gcd(up, down) = 1 and not up = down = 1, ceil(ntaps / up) <= 1024, 1 <= nch <=
+ * SDDC_DDC_MAX_CHANNELS; a violation returns SDDC_ERR_ARG.  NULL or ntaps == 0 turns the resampler
+ * off and frees its state.  Every set call copies the taps, sizes the tails, zeroes them and sets
+ * the position to 0.  A change waits for the handle's resampler launches in flight. */
+int sddc_ddc_set_channel_resampler(sddc_ddc_t *h, const float *taps, int ntaps, int up, int down, int nch);
+/* zero every channel's tail and the position: the next call starts a new stream (SDDC_ERR_STATE:
+ * no resampler set) */
+int sddc_ddc_channel_resampler_reset(sddc_ddc_t *h);
+/* ceil((pos+nsamp)*up/down) - ceil(pos*up/down) for any pos; 0 on factors outside the ranges above
+ * or nsamp > 2^40 */
+size_t sddc_ddc_resample_count(int up, int down, uint64_t pos, size_t nsamp);
+/* what the handle's NEXT call of nsamp samples would produce per channel (0 also: no resampler set) */
+size_t sddc_ddc_channel_resample_samples(sddc_ddc_t *h, size_t nsamp);
+/* GPU handles; enqueued on hip_stream, returns after launch.  *nout (may be NULL) receives the
+ * call's outputs per channel; d_out needs room for them (channel_resample_samples beforehand).
+ * SDDC_ERR_STATE: no resampler set, another nch than the set one, a CPU handle.  SDDC_ERR_ARG:
+ * nsamp == 0, a bad stride or alignment, a null buffer.  A failed call changes no state.  The calls
+ * of one handle share the tails and the position: they run one after the other in call order,
+ * whatever their streams. */
+int sddc_ddc_channel_resample_device(sddc_ddc_t *h, const void *d_iq, int nch, size_t nsamp, size_t in_stride,
+                                     float *d_out, size_t out_stride, size_t *nout, void *hip_stream);
+/* Host buffers, the same layouts.  GPU handle: copy in, kernel, copy back, synchronous; it advances
+ * the same device tails and position as the device call.  CPU handle: the AVX2 backend, the same
+ * definition and bound (another fixed order of the sum, also independent of the cut). */
+int sddc_ddc_channel_resample_host(sddc_ddc_t *h, const void *iq, int nch, size_t nsamp, size_t in_stride,
+                                   float *out, size_t out_stride, size_t *nout);
 
 /* ---- ingest ---------------------------------------
  * Pin a caller-owned host region (hipHostRegister) so the host path DMAs blocks
