@@ -320,11 +320,12 @@ void R2iq::channel_spectrum(const void *iq, bool cs16, int nch, size_t stride, i
     }
 }
 
-// The channel decimator (sddc_ddc_channel_decimate_host on a CPU handle).  Per channel the stream
-// [tail | the call's samples] is split into I and Q rows, and output m is the dot product of the
-// reversed taps g[k] = h[L - k] with the ntaps values from sample m R on: eight lane sums of
-// explicit FMAs over k = 8 i + lane, added in a fixed tree, then the last ntaps mod 8 taps one by
-// one.  The order depends on k alone, so any cut of a stream into calls gives the same bits.
+// The channel stream stages (sddc_ddc_channel_{decimate,resample}_host on a CPU handle) share three
+// steps.  split_stream: per channel the stream [tail | the call's samples] is split into I and Q
+// rows.  dot_iq: an output is the dot product of n reversed taps with n consecutive values of the
+// rows: eight lane sums of explicit FMAs over k = 8 i + lane, added in a fixed tree, then the last
+// n mod 8 taps one by one.  keep_tail: the last H values of the rows are the next call's tail.
+// The order depends on the tap index alone, so any cut of a stream into calls gives the same bits.
 static inline float hsum8(__m256 v)
 {
     const __m128 s4 = _mm_add_ps(_mm256_castps256_ps128(v), _mm256_extractf128_ps(v, 1));
@@ -332,6 +333,57 @@ static inline float hsum8(__m256 v)
     return _mm_cvtss_f32(_mm_add_ss(s2, _mm_shuffle_ps(s2, s2, 1)));
 }
 
+// x: the channel's first component of the call; tl: its H kept values; xr, xi: H + nsamp floats each
+static void split_stream(const void *x, bool cs16, float inv_s, size_t nsamp, const float *tl, size_t H, float *xr,
+                         float *xi)
+{
+    for (size_t k = 0; k < H; k++) {
+        xr[k] = tl[2 * k];
+        xi[k] = tl[2 * k + 1];
+    }
+    if (cs16) {
+        const int16_t *v = static_cast<const int16_t *>(x);
+        for (size_t i = 0; i < nsamp; i++) {
+            xr[H + i] = (float)v[2 * i] * inv_s;
+            xi[H + i] = (float)v[2 * i + 1] * inv_s;
+        }
+    } else {
+        const float *v = static_cast<const float *>(x);
+        for (size_t i = 0; i < nsamp; i++) {
+            xr[H + i] = v[2 * i];
+            xi[H + i] = v[2 * i + 1];
+        }
+    }
+}
+
+static inline void dot_iq(const float *g, const float *pr, const float *pi, int n, float *y)
+{
+    __m256 ar = _mm256_setzero_ps(), ai = _mm256_setzero_ps();
+    int k = 0;
+    for (; k + 8 <= n; k += 8) {
+        const __m256 gv = _mm256_loadu_ps(g + k);
+        ar = _mm256_fmadd_ps(gv, _mm256_loadu_ps(pr + k), ar);
+        ai = _mm256_fmadd_ps(gv, _mm256_loadu_ps(pi + k), ai);
+    }
+    float sr = hsum8(ar), si = hsum8(ai);
+    for (; k < n; k++) {
+        sr = std::fmaf(g[k], pr[k], sr);
+        si = std::fmaf(g[k], pi[k], si);
+    }
+    y[0] = sr;
+    y[1] = si;
+}
+
+static void keep_tail(const float *xr, const float *xi, size_t nsamp, size_t H, float *tl)
+{
+    for (size_t k = 0; k < H; k++) {   // the last H values of [tail | samples]
+        tl[2 * k] = xr[nsamp + k];
+        tl[2 * k + 1] = xi[nsamp + k];
+    }
+}
+
+// The channel decimator: output m is the dot product of the reversed taps g[k] = h[L - k] with the
+// ntaps values from sample m R on.
 void R2iq::channel_decimate(const void *iq, bool cs16, float inv_s, int nch, size_t nsamp, size_t in_stride,
                             const float *taps, int ntaps, int R, float *tail, float *out, size_t out_stride)
 {
@@ -340,54 +392,18 @@ void R2iq::channel_decimate(const void *iq, bool cs16, float inv_s, int nch, siz
     for (int k = 0; k < ntaps; k++) g[(size_t)k] = taps[L - (size_t)k];
     for (int c = 0; c < nch; c++) {
         float *tl = tail + (size_t)c * L * 2;
-        for (size_t k = 0; k < L; k++) {
-            xr[k] = tl[2 * k];
-            xi[k] = tl[2 * k + 1];
-        }
-        if (cs16) {
-            const int16_t *x = static_cast<const int16_t *>(iq) + (size_t)c * in_stride;
-            for (size_t i = 0; i < nsamp; i++) {
-                xr[L + i] = (float)x[2 * i] * inv_s;
-                xi[L + i] = (float)x[2 * i + 1] * inv_s;
-            }
-        } else {
-            const float *x = static_cast<const float *>(iq) + (size_t)c * in_stride;
-            for (size_t i = 0; i < nsamp; i++) {
-                xr[L + i] = x[2 * i];
-                xi[L + i] = x[2 * i + 1];
-            }
-        }
+        split_stream(static_cast<const char *>(iq) + (size_t)c * in_stride * (cs16 ? 2 : 4), cs16, inv_s, nsamp, tl, L,
+                     xr.data(), xi.data());
         float *y = out + (size_t)c * out_stride;
-        for (size_t m = 0; m < nout; m++) {
-            const float *pr = xr.data() + m * (size_t)R, *pi = xi.data() + m * (size_t)R;
-            __m256 ar = _mm256_setzero_ps(), ai = _mm256_setzero_ps();
-            int k = 0;
-            for (; k + 8 <= ntaps; k += 8) {
-                const __m256 gv = _mm256_loadu_ps(g.data() + k);
-                ar = _mm256_fmadd_ps(gv, _mm256_loadu_ps(pr + k), ar);
-                ai = _mm256_fmadd_ps(gv, _mm256_loadu_ps(pi + k), ai);
-            }
-            float sr = hsum8(ar), si = hsum8(ai);
-            for (; k < ntaps; k++) {
-                sr = std::fmaf(g[(size_t)k], pr[k], sr);
-                si = std::fmaf(g[(size_t)k], pi[k], si);
-            }
-            y[2 * m] = sr;
-            y[2 * m + 1] = si;
-        }
-        for (size_t k = 0; k < L; k++) {   // the last L values of [tail | samples]
-            tl[2 * k] = xr[nsamp + k];
-            tl[2 * k + 1] = xi[nsamp + k];
-        }
+        for (size_t m = 0; m < nout; m++)
+            dot_iq(g.data(), xr.data() + m * (size_t)R, xi.data() + m * (size_t)R, ntaps, y + 2 * m);
+        keep_tail(xr.data(), xi.data(), nsamp, L, tl);
     }
 }
 
-// The channel resampler (sddc_ddc_channel_resample_host on a CPU handle).  Per channel the stream
-// [tail | the call's samples] is split into I and Q rows; output k of the call has e + k M = s L + p
-// and is the dot product of phase p's reversed taps r_p[i] = h[p + (K - 1 - i) L] with the K values
-// from sample s - (K - 1) on: eight lane sums of explicit FMAs over i = 8 n + lane, added in a fixed
-// tree, then the last K mod 8 one by one.  The order depends on (p, i, K) alone, so any cut of a
-// stream into calls, at any position, gives the same bits.
+// The channel resampler: output k of the call has e + k M = s L + p and is the dot product of phase
+// p's reversed taps r_p[i] = h[p + (K - 1 - i) L] with the K values from sample s - (K - 1) on.  The
+// order depends on (p, i, K) alone, so the position does not change the bits either.
 void R2iq::channel_resample(const void *iq, bool cs16, float inv_s, int nch, size_t nsamp, size_t in_stride,
                             const float *taps, int ntaps, int L, int M, int e, size_t nout, float *tail, float *out,
                             size_t out_stride)
@@ -402,23 +418,8 @@ void R2iq::channel_resample(const void *iq, bool cs16, float inv_s, int nch, siz
         }
     for (int c = 0; c < nch; c++) {
         float *tl = tail + (size_t)c * H * 2;
-        for (size_t k = 0; k < H; k++) {
-            xr[k] = tl[2 * k];
-            xi[k] = tl[2 * k + 1];
-        }
-        if (cs16) {
-            const int16_t *x = static_cast<const int16_t *>(iq) + (size_t)c * in_stride;
-            for (size_t i = 0; i < nsamp; i++) {
-                xr[H + i] = (float)x[2 * i] * inv_s;
-                xi[H + i] = (float)x[2 * i + 1] * inv_s;
-            }
-        } else {
-            const float *x = static_cast<const float *>(iq) + (size_t)c * in_stride;
-            for (size_t i = 0; i < nsamp; i++) {
-                xr[H + i] = x[2 * i];
-                xi[H + i] = x[2 * i + 1];
-            }
-        }
+        split_stream(static_cast<const char *>(iq) + (size_t)c * in_stride * (cs16 ? 2 : 4), cs16, inv_s, nsamp, tl, H,
+                     xr.data(), xi.data());
         float *y = out + (size_t)c * out_stride;
         uint64_t s = (uint64_t)e / (uint64_t)L;   // output k's sample and phase, stepped by M / L
         int p = e % L;
@@ -426,21 +427,7 @@ void R2iq::channel_resample(const void *iq, bool cs16, float inv_s, int nch, siz
         const int dp = M % L;
         for (size_t m = 0; m < nout; m++) {
             // row index H + s - (K - 1) = s
-            const float *pr = xr.data() + s, *pi = xi.data() + s, *gp = g.data() + (size_t)p * (size_t)K;
-            __m256 ar = _mm256_setzero_ps(), ai = _mm256_setzero_ps();
-            int k = 0;
-            for (; k + 8 <= K; k += 8) {
-                const __m256 gv = _mm256_loadu_ps(gp + k);
-                ar = _mm256_fmadd_ps(gv, _mm256_loadu_ps(pr + k), ar);
-                ai = _mm256_fmadd_ps(gv, _mm256_loadu_ps(pi + k), ai);
-            }
-            float sr = hsum8(ar), si = hsum8(ai);
-            for (; k < K; k++) {
-                sr = std::fmaf(gp[k], pr[k], sr);
-                si = std::fmaf(gp[k], pi[k], si);
-            }
-            y[2 * m] = sr;
-            y[2 * m + 1] = si;
+            dot_iq(g.data() + (size_t)p * (size_t)K, xr.data() + s, xi.data() + s, K, y + 2 * m);
             s += ds;
             p += dp;
             if (p >= L) {
@@ -448,10 +435,7 @@ void R2iq::channel_resample(const void *iq, bool cs16, float inv_s, int nch, siz
                 s++;
             }
         }
-        for (size_t k = 0; k < H; k++) {   // the last H values of [tail | samples]
-            tl[2 * k] = xr[nsamp + k];
-            tl[2 * k + 1] = xi[nsamp + k];
-        }
+        keep_tail(xr.data(), xi.data(), nsamp, H, tl);
     }
 }
 

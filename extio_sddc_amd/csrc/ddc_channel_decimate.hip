@@ -6,12 +6,10 @@
 //   y_c[m] = v_c[m R]
 //
 // Work item: one (channel, tile) of `tile` <= kChDecTile outputs, taken by a 256-thread workgroup:
-//   stage    the tile's tile R + ntaps - 1 sample values go to LDS as float2: the samples of earlier
-//            calls from the handle's tail (8 bytes per lane), the call's own from global memory in
-//            aligned 16-byte loads (consecutive lanes consecutive addresses; the vectors that
-//            straddle the tile's ends are read sample by sample, so nothing outside the stream is
-//            touched), CS16 unpacked with integer ops and scaled by 1 / cs16_scale.  Sample p of
-//            the tile is stored polyphase-transposed at (p mod R) pitch + p div R, so that
+//   stage    the tile's tile R + ntaps - 1 sample values go to LDS as float2 and the stream's last
+//            ntaps - 1 to the handle's tail, as channel_stage.hpp describes (at most 10 16-byte
+//            loads per thread).  Sample p of the tile is stored polyphase-transposed at
+//            (p mod R) pitch + p div R, so that
 //   compute  output o reads tap j's sample (o R + L - j, L = ntaps - 1) at
 //            ((L - j) mod R) pitch + (L - j) div R + o: the lanes of a wave read consecutive float2
 //            for every tap (ds_read_b64, conflict-free for any pitch).  The taps are walked phase by
@@ -20,11 +18,6 @@
 //            tile of more than 256 outputs) and shares each tap between them; the tap index is
 //            uniform, so the taps come through scalar loads, eight per trip, from a copy the host
 //            has put in the walk's order.
-// A thread issues all its 16-byte loads of the tile (at most 10) before it uses the first, so a
-// workgroup has its whole tile in flight.
-// The stage also writes the new tail: stream sample i of the last L goes to tail_out, written by
-// the tile that owns it (samples of earlier calls: tile 0), read from tail_in — two buffers that
-// the host swaps per call, so no workgroup reads a tail another one is writing.
 //
 // Determinism: with k = L - j = q R + r, an output is the fixed sequence
 //   a[q mod 4] = fma(h[j], x[mR - j], a[q mod 4])  for r = 0 .. R - 1, q = 0, 1, ..   y = (a0 + a1) + (a2 + a3)
@@ -39,16 +32,13 @@
 // stores nothing.
 #include <hip/hip_runtime.h>
 
+#include "channel_stage.hpp"
 #include "ddc_kernels.h"
 
 namespace sddc {
 namespace {
 
-constexpr int NT = 256;
-
-// one LDS read per instruction (ddc_frame_common.hpp XRD: the compiler's ds_read2 pairs cost 8
-// LDS cycles against 2 for a ds_read_b64)
-#define CDC_RD(dst, expr) do { dst = (expr); asm volatile("" ::: "memory"); } while (0)
+using namespace chstage;
 
 struct Args {
     long long nsamp, nout, tiles, nitems;   // per channel: samples, outputs, tiles; items of the call
@@ -57,24 +47,6 @@ struct Args {
     unsigned rmagic;                        // ceil(2^32 / R): p div R = umulhi(p, rmagic) for p < 2^16
     float inv_s;                            // CS16: 1 / cs16_scale
 };
-
-template <bool CS16> struct Fmt;
-template <> struct Fmt<false> {
-    using Sample = float2;   // (I, Q) floats
-    using Vec = float4;      // 2 samples
-    static constexpr int V = 2;
-};
-template <> struct Fmt<true> {
-    using Sample = int;      // (I, Q) int16 in one dword, I in the low half
-    using Vec = int4;        // 4 samples
-    static constexpr int V = 4;
-};
-
-__device__ __forceinline__ float2 to_value(float2 x, float) { return x; }
-__device__ __forceinline__ float2 to_value(int x, float inv_s)
-{
-    return make_float2((float)(int)(short)(x & 0xffff) * inv_s, (float)(x >> 16) * inv_s);
-}
 
 // The sums of outputs tid (and tid + NT for NO = 2) of a staged tile.  The taps arrive in the
 // kernel's order (channel_decimate_order_taps): phase r = 0 .. min(R, ntaps) - 1 of the tile's rows,
@@ -229,23 +201,6 @@ __global__ __launch_bounds__(NT) void channel_decimate_kernel(const void *__rest
     }
 }
 
-template <bool CS16>
-hipError_t launch_fmt(const KernelTables &t, const void *d_iq, float *d_out, const float *d_taps,
-                      const float2 *d_tail_in, float2 *d_tail_out, const Args &a, int max_wgs, int device,
-                      hipStream_t s)
-{
-    auto kern = channel_decimate_kernel<CS16>;
-    int occ = 0, cus = 0;
-    hipError_t e = launch_geometry(t.lc, reinterpret_cast<const void *>(kern), NT, device, &occ, &cus);
-    if (e != hipSuccess) return e;
-    // one workgroup per item, or full residency with a loop
-    long long grid = a.nitems;
-    if (grid > (long long)cus * occ) grid = (long long)cus * occ;
-    if (max_wgs > 0 && grid > max_wgs) grid = max_wgs;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NT), 0, s, d_iq, d_out, d_taps, d_tail_in, d_tail_out, a);
-    return hipGetLastError();
-}
-
 }  // namespace
 
 ChDecLayout channel_decimate_layout(int R, int ntaps, int cs16)
@@ -256,28 +211,7 @@ ChDecLayout channel_decimate_layout(int R, int ntaps, int cs16)
     if (g.tile > kChDecTile) g.tile = kChDecTile;
     if (g.tile > 64) g.tile &= ~63;   // whole waves
     const int need = g.tile + hrows;
-    // The stage's stores: lane l of a 16-lane group holds samples V l + e (V = 2 CF32, 4 CS16) and
-    // stores e with one ds_write_b64, banked on the float2 index mod 16.  Take the pitch in
-    // [need, need + pad] with the fewest extra LDS cycles (tools/channel_decimate_banks.py).
-    const int V = cs16 ? 4 : 2;
-    int best = -1;
-    for (int pitch = need; pitch <= need + kChDecPitchPad; pitch++) {
-        int cost = 0;
-        for (int e = 0; e < V; e++)
-            for (int g0 = 0; g0 < 64; g0 += 16) {
-                int cnt[16] = {}, worst = 0;
-                for (int l = g0; l < g0 + 16; l++) {
-                    const int p = V * l + e, k = ((p % R) * pitch + p / R) & 15;
-                    if (++cnt[k] > worst) worst = cnt[k];
-                }
-                cost += worst - 1;
-            }
-        if (best < 0 || cost < best) {
-            best = cost;
-            g.pitch = pitch;
-        }
-    }
-    g.store_conflicts = best;
+    g.pitch = polyphase_pitch(R, need, need + kChDecPitchPad, cs16 ? 4 : 2, &g.store_conflicts);
     return g;
 }
 
@@ -311,8 +245,8 @@ hipError_t launch_channel_decimate(const KernelTables &t, const void *d_iq, int 
     a.pitch = g.pitch;
     a.rmagic = (unsigned)((0x100000000ULL + (unsigned)R - 1) / (unsigned)R);
     a.inv_s = cs16 ? (float)(1.0 / (double)cs16_scale) : 1.f;
-    return cs16 ? launch_fmt<true>(t, d_iq, d_out, d_taps, d_tail_in, d_tail_out, a, max_wgs, device, s)
-                : launch_fmt<false>(t, d_iq, d_out, d_taps, d_tail_in, d_tail_out, a, max_wgs, device, s);
+    return cs16 ? launch_stage(t, channel_decimate_kernel<true>, d_iq, d_out, d_taps, d_tail_in, d_tail_out, a, max_wgs, device, s)
+                : launch_stage(t, channel_decimate_kernel<false>, d_iq, d_out, d_taps, d_tail_in, d_tail_out, a, max_wgs, device, s);
 }
 
 }  // namespace sddc

@@ -14,12 +14,9 @@
 //
 // Work item: one (channel, tile) of `ta` consecutive a (ta L outputs), taken by a 256-thread workgroup:
 //   stage    the tile's ta M + K - 1 sample values (the last tile: up to the call's end) go to LDS as
-//            float2, exactly as in ddc_channel_decimate.hip: the samples of earlier calls from the
-//            handle's tail, the call's own from global memory in aligned 16-byte loads that are all
-//            issued before the first is used (the vectors that straddle the tile's ends are read
-//            sample by sample, so nothing outside the stream is touched), CS16 unpacked with integer
-//            ops and scaled by 1 / cs16_scale.  Sample position s of the tile is stored
-//            polyphase-transposed by M at (s mod M) pitch + s div M, so that
+//            float2 and the stream's last K - 1 to the handle's tail, as channel_stage.hpp describes.
+//            Sample position s of the tile is stored polyphase-transposed by M at
+//            (s mod M) pitch + s div M, so that
 //   compute  the 32 lanes of a half wave hold one b and 32 consecutive a, and read consecutive
 //            float2 for every tap: ds_read_b64 is served in the lane groups {0-31} and {32-63}, each
 //            conflict-free on 64 consecutive dwords whatever the row.  The unit of work is such a
@@ -29,10 +26,8 @@
 //            picks its half's with one select.  Tap j of lane (a, b) reads position
 //            a M + o_b + K - 1 - j: the row steps down by one per tap and wraps to the previous
 //            column.  Sixteen reads are issued before the first fma.
-// The stage also writes the new tail: stream sample i of the last K - 1 goes to tail_out, written by
-// the tile that owns it (samples of earlier calls: tile 0; the samples past the last output: the
-// last tile), read from tail_in — two buffers that the host swaps per call.  A call without an
-// output (M > L, a short call) still has one item, which only moves the tail.
+// The samples past the call's last output belong to the last tile, which so writes them to the new
+// tail.  A call without an output (M > L, a short call) still has one item, which only moves the tail.
 //
 // Determinism: an output is the fixed sequence
 //   a[j mod 4] = fma(g_p[j], x[s - j], a[j mod 4])   for j = 0, 1, .. K - 1;   y = (a0 + a1) + (a2 + a3)
@@ -45,17 +40,15 @@
 
 #include <type_traits>
 
+#include "channel_stage.hpp"
 #include "ddc_kernels.h"
 
 namespace sddc {
 namespace {
 
-constexpr int NT = 256;
-constexpr int NW = NT / 64;
+using namespace chstage;
 
-// one LDS read per instruction (ddc_frame_common.hpp XRD: the compiler's ds_read2 pairs cost 8
-// LDS cycles against 2 for a ds_read_b64)
-#define CDC_RD(dst, expr) do { dst = (expr); asm volatile("" ::: "memory"); } while (0)
+constexpr int NW = NT / 64;
 
 struct Args {
     long long nsamp, nout, na, tiles, nitems;   // per channel: samples, outputs, values of a, tiles; items of the call
@@ -65,24 +58,6 @@ struct Args {
     unsigned mmagic;                            // ceil(2^32 / M): s div M = umulhi(s, mmagic) for s < 2^16; 0: M = 1
     float inv_s;                                // CS16: 1 / cs16_scale
 };
-
-template <bool CS16> struct Fmt;
-template <> struct Fmt<false> {
-    using Sample = float2;   // (I, Q) floats
-    using Vec = float4;      // 2 samples
-    static constexpr int V = 2;
-};
-template <> struct Fmt<true> {
-    using Sample = int;      // (I, Q) int16 in one dword, I in the low half
-    using Vec = int4;        // 4 samples
-    static constexpr int V = 4;
-};
-
-__device__ __forceinline__ float2 to_value(float2 x, float) { return x; }
-__device__ __forceinline__ float2 to_value(int x, float inv_s)
-{
-    return make_float2((float)(int)(short)(x & 0xffff) * inv_s, (float)(x >> 16) * inv_s);
-}
 
 // s div M for s < 2^16 (M = 1 has no 32-bit magic: mmagic = 0 stands for it)
 __device__ __forceinline__ unsigned div_m(unsigned s, unsigned mmagic) { return mmagic ? __umulhi(s, mmagic) : s; }
@@ -259,23 +234,6 @@ __global__ __launch_bounds__(NT) void channel_resample_kernel(const void *__rest
     }
 }
 
-template <bool CS16>
-hipError_t launch_fmt(const KernelTables &t, const void *d_iq, float *d_out, const float *d_taps,
-                      const float2 *d_tail_in, float2 *d_tail_out, const Args &a, int max_wgs, int device,
-                      hipStream_t s)
-{
-    auto kern = channel_resample_kernel<CS16>;
-    int occ = 0, cus = 0;
-    hipError_t e = launch_geometry(t.lc, reinterpret_cast<const void *>(kern), NT, device, &occ, &cus);
-    if (e != hipSuccess) return e;
-    // one workgroup per item, or full residency with a loop
-    long long grid = a.nitems;
-    if (grid > (long long)cus * occ) grid = (long long)cus * occ;
-    if (max_wgs > 0 && grid > max_wgs) grid = max_wgs;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NT), 0, s, d_iq, d_out, d_taps, d_tail_in, d_tail_out, a);
-    return hipGetLastError();
-}
-
 }  // namespace
 
 ChResLayout channel_resample_layout(int L, int M, int ntaps, int cs16)
@@ -289,29 +247,9 @@ ChResLayout channel_resample_layout(int L, int M, int ntaps, int cs16)
     if (g.ta > kChResMaxA) g.ta = kChResMaxA;
     if (g.ta < 1) return g;
     const int need = g.ta + hcols;
-    // The stage's stores: lane l of a 16-lane group holds samples V l + e (V = 2 CF32, 4 CS16) and
-    // stores e with one ds_write_b64, banked on the float2 index mod 16.  Take the pitch in
-    // [need, need + pad] that the LDS holds with the fewest extra LDS cycles
-    // (tools/channel_resample_banks.py).
-    const int V = cs16 ? 4 : 2;
-    int best = -1;
-    for (int pitch = need; pitch <= need + kChResPitchPad && pitch <= room; pitch++) {
-        int cost = 0;
-        for (int e = 0; e < V; e++)
-            for (int g0 = 0; g0 < 64; g0 += 16) {
-                int cnt[16] = {}, worst = 0;
-                for (int l = g0; l < g0 + 16; l++) {
-                    const int p = V * l + e, k = ((p % M) * pitch + p / M) & 15;
-                    if (++cnt[k] > worst) worst = cnt[k];
-                }
-                cost += worst - 1;
-            }
-        if (best < 0 || cost < best) {
-            best = cost;
-            g.pitch = pitch;
-        }
-    }
-    g.store_conflicts = best;
+    // a pitch that the LDS holds
+    const int top = need + kChResPitchPad < room ? need + kChResPitchPad : room;
+    g.pitch = polyphase_pitch(M, need, top, cs16 ? 4 : 2, &g.store_conflicts);
     return g;
 }
 
@@ -354,8 +292,8 @@ hipError_t launch_channel_resample(const KernelTables &t, const void *d_iq, int 
     a.pitch = g.pitch;
     a.mmagic = M == 1 ? 0u : (unsigned)((0x100000000ULL + (unsigned)M - 1) / (unsigned)M);
     a.inv_s = cs16 ? (float)(1.0 / (double)cs16_scale) : 1.f;
-    return cs16 ? launch_fmt<true>(t, d_iq, d_out, d_taps, d_tail_in, d_tail_out, a, max_wgs, device, s)
-                : launch_fmt<false>(t, d_iq, d_out, d_taps, d_tail_in, d_tail_out, a, max_wgs, device, s);
+    return cs16 ? launch_stage(t, channel_resample_kernel<true>, d_iq, d_out, d_taps, d_tail_in, d_tail_out, a, max_wgs, device, s)
+                : launch_stage(t, channel_resample_kernel<false>, d_iq, d_out, d_taps, d_tail_in, d_tail_out, a, max_wgs, device, s);
 }
 
 }  // namespace sddc

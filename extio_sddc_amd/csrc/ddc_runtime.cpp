@@ -18,6 +18,7 @@
 #include <mutex>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "cpu/r2iq_cpu.h"
@@ -137,6 +138,71 @@ struct Readers {
     {
         for (auto &p : v) (void)hipEventDestroy(p.second);
         v.clear();
+    }
+};
+
+// The state of a streaming channel stage (the channel decimator, the channel resampler): the taps
+// (empty = off) with the channel count, their device copy in the kernel's order, and each
+// channel's last H sample values as float2 in two device buffers: a launch reads d_tail[cur] and
+// writes the other one, and the host swaps them after it.  The tails are per handle, so every
+// launch first waits for the other streams' last launches (readers).  A CPU handle keeps the
+// tails in tail_h.  d_in / d_out are the host call's device buffers, grown on demand.
+// Every member function runs under the handle's mu.
+struct ChannelStream {
+    std::vector<float> taps;
+    int nch = 0, H = 0;
+    float *d_taps = nullptr;
+    size_t taps_cap = 0;                   // floats
+    float2 *d_tail[2] = {};                // [nch][H] each
+    int cur = 0;
+    std::vector<float> tail_h;             // CPU handle: [nch][H][2]
+    Readers readers;
+    int max_wgs = 0;
+    void *d_in = nullptr;
+    float *d_out = nullptr;
+    size_t in_cap = 0, out_cap = 0;        // bytes, floats
+
+    // off: no taps, no tails (the caller has waited for the launches in flight)
+    void clear()
+    {
+        taps.clear();
+        nch = H = 0;
+        tail_h.clear();
+        for (float2 *&p : d_tail) {
+            if (p) (void)hipFree(p);
+            p = nullptr;
+        }
+        cur = 0;
+    }
+    void free_all()
+    {
+        clear();
+        if (d_taps) (void)hipFree(d_taps);
+        if (d_in) (void)hipFree(d_in);
+        if (d_out) (void)hipFree(d_out);
+        d_taps = nullptr;
+        d_in = nullptr;
+        d_out = nullptr;
+        taps_cap = in_cap = out_cap = 0;
+        readers.clear();
+    }
+    // Validated taps (null or ntaps == 0: off) with their `nordered` floats in the kernel's order
+    // and H_ kept values for each of nch_ channels; the tails start as zeros.
+    int configure(sddc_ddc *h, const char *name, const float *t, int ntaps, const float *ordered, size_t nordered,
+                  int H_, int nch_);
+    int reset(sddc_ddc *h);   // the tails back to zeros
+    // One launch on s, fn(tail_in, tail_out): it reads the current tails and writes the other
+    // buffer, so it runs after every earlier launch of the handle, whatever its stream; the buffers
+    // swap once it is enqueued.
+    template <class F> int launch(hipStream_t s, F fn)
+    {
+        HIP_TRY(readers.order_before(s));
+        const hipError_t e = fn(d_tail[cur], d_tail[cur ^ 1]);
+        const hipError_t er = readers.record(s);   // whatever was enqueued stays ordered
+        HIP_TRY(e);
+        if (H > 0) cur ^= 1;
+        HIP_TRY(er);
+        return SDDC_OK;
     }
 };
 
@@ -300,38 +366,14 @@ struct sddc_ddc {
     Readers chsp_readers;
     int chsp_max_wgs = 0;                  // SDDC_DDC_PARAM_CHSPEC_MAX_WGS
 
-    // channel decimator (sddc_ddc_channel_decimate_*): the taps (empty = off) with the factor and the
-    // channel count, their device copy, and each channel's last ntaps - 1 sample values as float2 in
-    // two device buffers: a launch reads d_chdec_tail[chdec_cur] and writes the other one, and the
-    // host swaps them after it.  The tails are per handle, so every launch first waits for the other
-    // streams' last launches (chdec_readers).  A CPU handle keeps the tails in chdec_tail_h.
-    std::vector<float> chdec_taps;
-    int chdec_R = 0, chdec_nch = 0;
-    float *d_chdec_taps = nullptr;         // [SDDC_DDC_DECIM_MAX_TAPS]
-    float2 *d_chdec_tail[2] = {};          // [chdec_nch][ntaps - 1] each
-    int chdec_cur = 0;
-    std::vector<float> chdec_tail_h;       // CPU handle: [chdec_nch][ntaps - 1][2]
-    void *d_chdec_in = nullptr;            // channel_decimate_host
-    float *d_chdec_out = nullptr;
-    size_t chdec_in_cap = 0, chdec_out_cap = 0;   // bytes, floats
-    Readers chdec_readers;
-    int chdec_max_wgs = 0;                 // SDDC_DDC_PARAM_CHDEC_MAX_WGS
-
-    // channel resampler (sddc_ddc_channel_resample_*): as the decimator's state, with K - 1 =
-    // ceil(ntaps / up) - 1 kept values per channel, and the stream position reduced to chres_e =
-    // m0 down - N up (0 <= chres_e < down) for N samples consumed and m0 = ceil(N up / down)
+    // channel decimator and channel resampler (sddc_ddc_channel_{decimate,resample}_*): one
+    // ChannelStream each, with H = ntaps - 1 and H = K - 1 = ceil(ntaps / up) - 1 kept values per
+    // channel, and what the stage alone owns.  The resampler's stream position is reduced to chres_e
+    // = m0 down - N up (0 <= chres_e < down) for N samples consumed and m0 = ceil(N up / down)
     // outputs produced: all a call needs, and no product overflows at any stream length.
-    std::vector<float> chres_taps;
-    int chres_L = 0, chres_M = 0, chres_K = 0, chres_nch = 0, chres_e = 0;
-    float *d_chres_taps = nullptr;         // [up][K] in the kernel's order
-    float2 *d_chres_tail[2] = {};          // [chres_nch][K - 1] each
-    int chres_cur = 0;
-    std::vector<float> chres_tail_h;       // CPU handle: [chres_nch][K - 1][2]
-    void *d_chres_in = nullptr;            // channel_resample_host
-    float *d_chres_out = nullptr;
-    size_t chres_in_cap = 0, chres_out_cap = 0;   // bytes, floats
-    Readers chres_readers;
-    int chres_max_wgs = 0;                 // SDDC_DDC_PARAM_CHRES_MAX_WGS
+    ChannelStream chdec, chres;            // max_wgs: SDDC_DDC_PARAM_CH{DEC,RES}_MAX_WGS
+    int chdec_R = 0;
+    int chres_L = 0, chres_M = 0, chres_e = 0;
 
     // CPU handle (device SDDC_DDC_DEVICE_CPU): the AVX2 backend; no HIP object above exists
     std::unique_ptr<sddc::cpu::R2iq> cpu;
@@ -363,6 +405,139 @@ static bool injected_late_failure(sddc_ddc_t *h)
 {
     if (h->inject_late < 0) return false;
     return h->inject_late-- == 0;
+}
+
+// A host call's device buffer of at least `need` elements (bytes for a void buffer).  The earlier
+// host calls were synchronous: nothing reads the old buffer.
+template <class T>
+static int grow_device_buffer(T **ptr, size_t *cap, size_t need, const char *who, const char *what)
+{
+    if (need <= *cap) return SDDC_OK;
+    if (*ptr) (void)hipFree(*ptr);
+    *ptr = nullptr;
+    *cap = 0;
+    constexpr size_t elem = sizeof(std::conditional_t<std::is_void<T>::value, char, T>);
+    if (hipMalloc(ptr, need * elem) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(SDDC_ERR_NOMEM, "%s: no device memory for %zu %s", who, need, what);
+    }
+    *cap = need;
+    return SDDC_OK;
+}
+
+/* ---- the channel stream stages' shared state machine (ChannelStream) ---------------------- */
+int ChannelStream::configure(sddc_ddc_t *h, const char *name, const float *t, int ntaps, const float *ordered,
+                             size_t nordered, int H_, int nch_)
+{
+    const bool off = !t || ntaps == 0;
+    const size_t tail = off ? 0 : (size_t)nch_ * (size_t)H_;   // complex values
+    if (h->cpu) {
+        clear();
+        if (off) return SDDC_OK;
+        try {
+            tail_h.assign(2 * tail, 0.f);
+            taps.assign(t, t + ntaps);
+        } catch (const std::exception &ex) {
+            clear();
+            return fail(SDDC_ERR_NOMEM, "%s: %s", name, ex.what());
+        }
+        H = H_;
+        nch = nch_;
+        return SDDC_OK;
+    }
+    DeviceGuard g(h->device);
+    HIP_TRY(g.err);
+    HIP_TRY(readers.sync());   // earlier launches, on any stream, may still use the taps and the tails
+    clear();                   // a failed upload leaves the stage off
+    if (off) return SDDC_OK;
+    if (nordered > taps_cap) {
+        if (d_taps) (void)hipFree(d_taps);
+        d_taps = nullptr;
+        taps_cap = 0;
+        HIP_TRY(hipMalloc(&d_taps, nordered * sizeof(float)));
+        taps_cap = nordered;
+    }
+    HIP_TRY(hipMemcpy(d_taps, ordered, nordered * sizeof(float), hipMemcpyHostToDevice));
+    if (tail) {
+        for (float2 *&p : d_tail) {
+            if (hipMalloc(&p, tail * sizeof(float2)) != hipSuccess) {
+                (void)hipGetLastError();
+                p = nullptr;
+                clear();
+                return fail(SDDC_ERR_NOMEM, "%s: no device memory for %zu tail values", name, tail);
+            }
+        }
+        // zeroed on the handle's stream and waited for: the first launch may be on any stream
+        hipError_t e = hipMemsetAsync(d_tail[0], 0, tail * sizeof(float2), h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) {
+            clear();
+            HIP_TRY(e);
+        }
+    }
+    taps.assign(t, t + ntaps);
+    H = H_;
+    nch = nch_;
+    return SDDC_OK;
+}
+
+int ChannelStream::reset(sddc_ddc_t *h)
+{
+    if (h->cpu) {
+        std::fill(tail_h.begin(), tail_h.end(), 0.f);
+        return SDDC_OK;
+    }
+    const size_t tail = (size_t)nch * (size_t)H;
+    if (!tail) return SDDC_OK;
+    DeviceGuard g(h->device);
+    HIP_TRY(g.err);
+    HIP_TRY(readers.sync());   // earlier launches, on any stream, may still use the tails
+    HIP_TRY(hipMemsetAsync(d_tail[cur], 0, tail * sizeof(float2), h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // the next launch may be on any stream
+    return SDDC_OK;
+}
+
+// The stride, null and alignment checks of a stage's call (under h->mu: the format is read here);
+// out_need names 2 nout in the stage's terms.
+static int check_channel_io(const sddc_ddc_t *h, const char *out_need, const void *iq, int nch, size_t nsamp,
+                            size_t in_stride, const float *out, size_t out_stride, size_t nout)
+{
+    if (nch > 1 && (in_stride < 2 * nsamp || (in_stride & 1) != 0))
+        return fail(SDDC_ERR_ARG, "in_stride must be even and >= 2 nsamp (got %zu, nsamp %zu)", in_stride, nsamp);
+    if (nch > 1 && (out_stride < 2 * nout || (out_stride & 1) != 0))
+        return fail(SDDC_ERR_ARG, "out_stride must be even and >= %s (got %zu, need %zu)", out_need, out_stride, 2 * nout);
+    if (!iq || !out) return fail(SDDC_ERR_ARG, "null buffer");
+    const uintptr_t sample = h->out_fmt == SDDC_DDC_FMT_CS16 ? 4 : 8;
+    if (((uintptr_t)iq & (sample - 1)) != 0) return fail(SDDC_ERR_ARG, "iq must be %d-byte aligned", (int)sample);
+    if (((uintptr_t)out & 7) != 0) return fail(SDDC_ERR_ARG, "the output must be 8-byte aligned");
+    return SDDC_OK;
+}
+
+// A stage's host call on a GPU handle: the channels' samples to the device, launch(d_in, d_out) on
+// the handle's stream, the nout outputs of every channel back, and a wait for all of it.
+template <class F>
+static int channel_host_roundtrip(sddc_ddc_t *h, ChannelStream &st, const char *who, const void *iq, int nch,
+                                  size_t nsamp, size_t in_stride, float *out, size_t out_stride, size_t nout, F launch)
+{
+    DeviceGuard g(h->device);
+    HIP_TRY(g.err);
+    // the spans that hold every channel's samples and outputs (one float2 at least: a call without an output)
+    const size_t in_bytes = ((size_t)(nch - 1) * (nch > 1 ? in_stride : 0) + 2 * nsamp) *
+                            (h->out_fmt == SDDC_DDC_FMT_CS16 ? 2 : 4);
+    const size_t out_floats = (size_t)(nch - 1) * (nch > 1 ? out_stride : 0) + 2 * nout;
+    if (int rc = grow_device_buffer(&st.d_in, &st.in_cap, in_bytes, who, "input bytes")) return rc;
+    if (int rc = grow_device_buffer(&st.d_out, &st.out_cap, out_floats ? out_floats : 2, who, "output floats")) return rc;
+    HIP_TRY(hipMemcpyAsync(st.d_in, iq, in_bytes, hipMemcpyHostToDevice, h->stream));
+    const int rc = launch(st.d_in, st.d_out);
+    if (rc == SDDC_OK && nout) {   // the streams alone: the caller's memory between them stays as it is
+        if (nch == 1 || out_stride == 2 * nout)
+            HIP_TRY(hipMemcpyAsync(out, st.d_out, out_floats * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        else
+            HIP_TRY(hipMemcpy2DAsync(out, out_stride * sizeof(float), st.d_out, out_stride * sizeof(float),
+                                     2 * nout * sizeof(float), (size_t)nch, hipMemcpyDeviceToHost, h->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(h->stream));   // also after a failed launch: the caller's input is free again
+    return rc;
 }
 
 extern "C" {
@@ -548,8 +723,8 @@ int sddc_ddc_destroy(sddc_ddc_t *h)
         (void)h->ch_readers.sync();
         (void)h->sp_readers.sync();
         (void)h->chsp_readers.sync();
-        (void)h->chdec_readers.sync();
-        (void)h->chres_readers.sync();
+        (void)h->chdec.readers.sync();
+        (void)h->chres.readers.sync();
         if (h->d_tables) (void)hipFree(h->d_tables);
         for (auto &sl : h->hs) {
             if (sl.d_in) (void)hipFree(sl.d_in);
@@ -581,18 +756,8 @@ int sddc_ddc_destroy(sddc_ddc_t *h)
         if (h->d_chsp_in) (void)hipFree(h->d_chsp_in);
         if (h->d_chsp_out) (void)hipFree(h->d_chsp_out);
         h->chsp_readers.clear();
-        if (h->d_chdec_taps) (void)hipFree(h->d_chdec_taps);
-        for (float2 *p : h->d_chdec_tail)
-            if (p) (void)hipFree(p);
-        if (h->d_chdec_in) (void)hipFree(h->d_chdec_in);
-        if (h->d_chdec_out) (void)hipFree(h->d_chdec_out);
-        h->chdec_readers.clear();
-        if (h->d_chres_taps) (void)hipFree(h->d_chres_taps);
-        for (float2 *p : h->d_chres_tail)
-            if (p) (void)hipFree(p);
-        if (h->d_chres_in) (void)hipFree(h->d_chres_in);
-        if (h->d_chres_out) (void)hipFree(h->d_chres_out);
-        h->chres_readers.clear();
+        h->chdec.free_all();
+        h->chres.free_all();
         if (h->fsa.h_ring) (void)hipHostFree(h->fsa.h_ring);   // its writers were waited for above
         h->readers.clear();
         h->ch_readers.clear();
@@ -1109,11 +1274,11 @@ int sddc_ddc_internal_set_param(sddc_ddc_t *h, int param, int value)
         return SDDC_OK;
     case SDDC_DDC_PARAM_CHDEC_MAX_WGS:
         if (value < 0) return fail(SDDC_ERR_ARG, "channel decimator workgroup cap %d is negative", value);
-        h->chdec_max_wgs = value;
+        h->chdec.max_wgs = value;
         return SDDC_OK;
     case SDDC_DDC_PARAM_CHRES_MAX_WGS:
         if (value < 0) return fail(SDDC_ERR_ARG, "channel resampler workgroup cap %d is negative", value);
-        h->chres_max_wgs = value;
+        h->chres.max_wgs = value;
         return SDDC_OK;
     default:
         return fail(SDDC_ERR_ARG, "unknown parameter %d", param);
@@ -1627,27 +1792,10 @@ int sddc_ddc_channel_spectrum_host(sddc_ddc_t *h, const void *iq, int nch, size_
     // the span that holds every channel's nsamp samples, and the rows
     const size_t in_bytes = ((size_t)(nch - 1) * (nch > 1 ? in_stride : 0) + 2 * nsamp) * (cs16 ? 2 : 4);
     const size_t out_floats = (size_t)nch * (size_t)nrows * (size_t)n;
-    // the earlier host calls were synchronous: nothing reads the old buffers
-    if (in_bytes > h->chsp_in_cap) {
-        if (h->d_chsp_in) (void)hipFree(h->d_chsp_in);
-        h->d_chsp_in = nullptr;
-        h->chsp_in_cap = 0;
-        if (hipMalloc(&h->d_chsp_in, in_bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(SDDC_ERR_NOMEM, "channel_spectrum_host: no device memory for %zu input bytes", in_bytes);
-        }
-        h->chsp_in_cap = in_bytes;
-    }
-    if (out_floats > h->chsp_out_cap) {
-        if (h->d_chsp_out) (void)hipFree(h->d_chsp_out);
-        h->d_chsp_out = nullptr;
-        h->chsp_out_cap = 0;
-        if (hipMalloc(&h->d_chsp_out, out_floats * sizeof(float)) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(SDDC_ERR_NOMEM, "channel_spectrum_host: no device memory for %zu output floats", out_floats);
-        }
-        h->chsp_out_cap = out_floats;
-    }
+    if (int rc = grow_device_buffer(&h->d_chsp_in, &h->chsp_in_cap, in_bytes, "channel_spectrum_host", "input bytes"))
+        return rc;
+    if (int rc = grow_device_buffer(&h->d_chsp_out, &h->chsp_out_cap, out_floats, "channel_spectrum_host", "output floats"))
+        return rc;
     HIP_TRY(hipMemcpyAsync(h->d_chsp_in, iq, in_bytes, hipMemcpyHostToDevice, h->stream));
     const int rc = chsp_launch(h, h->d_chsp_in, nch, in_stride, n, hop, frames_per_row, nrows, h->d_chsp_out, h->stream);
     if (rc == SDDC_OK)
@@ -1659,19 +1807,6 @@ int sddc_ddc_channel_spectrum_host(sddc_ddc_t *h, const void *iq, int nch, size_
 /* ---- channel decimator: a streaming decimating FIR on the DDC's IQ output ----------------- */
 static_assert(SDDC_DDC_DECIM_MAX_TAPS == sddc::kChDecMaxTaps && SDDC_DDC_DECIM_MAX_FACTOR == sddc::kChDecMaxFactor,
               "the kernel's limits are the ABI's");
-
-// off: no taps, no tails (the caller holds h->mu and has waited for the launches in flight)
-static void chdec_clear(sddc_ddc_t *h)
-{
-    h->chdec_taps.clear();
-    h->chdec_R = h->chdec_nch = 0;
-    h->chdec_tail_h.clear();
-    for (float2 *&p : h->d_chdec_tail) {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    }
-    h->chdec_cur = 0;
-}
 
 /* internal (sddc_ddc_internal.h): the kernel's tile of (factor, ntaps, format) */
 int sddc_ddc_internal_chdec_layout(int factor, int ntaps, int cs16, int *tile, int *pitch, int *store_conflicts)
@@ -1690,6 +1825,7 @@ int sddc_ddc_set_channel_decimator(sddc_ddc_t *h, const float *taps, int ntaps, 
 {
     if (!h) return fail(SDDC_ERR_ARG, "null handle");
     const bool off = !taps || ntaps == 0;
+    float ordered[SDDC_DDC_DECIM_MAX_TAPS];   // the device copy is in the kernel's order
     if (!off) {
         if (ntaps < 1 || ntaps > SDDC_DDC_DECIM_MAX_TAPS)
             return fail(SDDC_ERR_ARG, "channel decimator: ntaps %d outside 1..%d", ntaps, SDDC_DDC_DECIM_MAX_TAPS);
@@ -1699,54 +1835,11 @@ int sddc_ddc_set_channel_decimator(sddc_ddc_t *h, const float *taps, int ntaps, 
             return fail(SDDC_ERR_ARG, "channel decimator: nch %d outside 1..%d", nch, SDDC_DDC_MAX_CHANNELS);
         for (int j = 0; j < ntaps; j++)
             if (!std::isfinite(taps[j])) return fail(SDDC_ERR_ARG, "channel decimator: tap %d is not finite", j);
+        sddc::channel_decimate_order_taps(taps, ntaps, factor, ordered);
     }
     std::lock_guard<std::mutex> lk(h->mu);
-    const size_t tail = off ? 0 : (size_t)nch * (size_t)(ntaps - 1);   // complex values
-    if (h->cpu) {
-        chdec_clear(h);
-        if (off) return SDDC_OK;
-        try {
-            h->chdec_tail_h.assign(2 * tail, 0.f);
-            h->chdec_taps.assign(taps, taps + ntaps);
-        } catch (const std::exception &ex) {
-            chdec_clear(h);
-            return fail(SDDC_ERR_NOMEM, "channel decimator: %s", ex.what());
-        }
-        h->chdec_R = factor;
-        h->chdec_nch = nch;
-        return SDDC_OK;
-    }
-    DeviceGuard g(h->device);
-    HIP_TRY(g.err);
-    HIP_TRY(h->chdec_readers.sync());   // earlier launches, on any stream, may still use the taps and the tails
-    chdec_clear(h);                     // a failed upload leaves the decimator off
-    if (off) return SDDC_OK;
-    if (!h->d_chdec_taps) HIP_TRY(hipMalloc(&h->d_chdec_taps, SDDC_DDC_DECIM_MAX_TAPS * sizeof(float)));
-    {   // the device copy is in the kernel's order
-        float ordered[SDDC_DDC_DECIM_MAX_TAPS];
-        sddc::channel_decimate_order_taps(taps, ntaps, factor, ordered);
-        HIP_TRY(hipMemcpy(h->d_chdec_taps, ordered, (size_t)ntaps * sizeof(float), hipMemcpyHostToDevice));
-    }
-    if (tail) {
-        for (float2 *&p : h->d_chdec_tail) {
-            if (hipMalloc(&p, tail * sizeof(float2)) != hipSuccess) {
-                (void)hipGetLastError();
-                p = nullptr;
-                chdec_clear(h);
-                return fail(SDDC_ERR_NOMEM, "channel decimator: no device memory for %zu tail values", tail);
-            }
-        }
-        // zeroed on the handle's stream and waited for: the first launch may be on any stream
-        hipError_t e = hipMemsetAsync(h->d_chdec_tail[0], 0, tail * sizeof(float2), h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) {
-            chdec_clear(h);
-            HIP_TRY(e);
-        }
-    }
-    h->chdec_taps.assign(taps, taps + ntaps);
-    h->chdec_R = factor;
-    h->chdec_nch = nch;
+    if (int rc = h->chdec.configure(h, "channel decimator", taps, ntaps, ordered, (size_t)ntaps, ntaps - 1, nch)) return rc;
+    h->chdec_R = off ? 0 : factor;
     return SDDC_OK;
 }
 
@@ -1754,19 +1847,8 @@ int sddc_ddc_channel_decimator_reset(sddc_ddc_t *h)
 {
     if (!h) return fail(SDDC_ERR_ARG, "null handle");
     std::lock_guard<std::mutex> lk(h->mu);
-    if (h->chdec_taps.empty()) return fail(SDDC_ERR_STATE, "channel decimator reset: no decimator set");
-    if (h->cpu) {
-        std::fill(h->chdec_tail_h.begin(), h->chdec_tail_h.end(), 0.f);
-        return SDDC_OK;
-    }
-    const size_t tail = (size_t)h->chdec_nch * (h->chdec_taps.size() - 1);
-    if (!tail) return SDDC_OK;
-    DeviceGuard g(h->device);
-    HIP_TRY(g.err);
-    HIP_TRY(h->chdec_readers.sync());   // earlier launches, on any stream, may still use the tails
-    HIP_TRY(hipMemsetAsync(h->d_chdec_tail[h->chdec_cur], 0, tail * sizeof(float2), h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));   // the next launch may be on any stream
-    return SDDC_OK;
+    if (h->chdec.taps.empty()) return fail(SDDC_ERR_STATE, "channel decimator reset: no decimator set");
+    return h->chdec.reset(h);
 }
 
 size_t sddc_ddc_channel_decimate_samples(int factor, size_t nsamp)
@@ -1779,41 +1861,24 @@ size_t sddc_ddc_channel_decimate_samples(int factor, size_t nsamp)
 static int check_chdec_args(const sddc_ddc_t *h, const void *iq, int nch, size_t nsamp, size_t in_stride,
                             const float *out, size_t out_stride)
 {
-    if (h->chdec_taps.empty()) return fail(SDDC_ERR_STATE, "channel decimate: no decimator set");
-    if (nch != h->chdec_nch)
+    if (h->chdec.taps.empty()) return fail(SDDC_ERR_STATE, "channel decimate: no decimator set");
+    if (nch != h->chdec.nch)
         return fail(SDDC_ERR_STATE, "channel decimate: the decimator is set for %d channels, the call has %d",
-                    h->chdec_nch, nch);
+                    h->chdec.nch, nch);
     const size_t R = (size_t)h->chdec_R;
     if (nsamp == 0 || nsamp % R != 0 || nsamp > ((size_t)1 << 40))
         return fail(SDDC_ERR_ARG, "nsamp must be a positive multiple of the factor %zu, at most 2^40 (got %zu)", R, nsamp);
-    if (nch > 1 && (in_stride < 2 * nsamp || (in_stride & 1) != 0))
-        return fail(SDDC_ERR_ARG, "in_stride must be even and >= 2 nsamp (got %zu, nsamp %zu)", in_stride, nsamp);
-    if (nch > 1 && (out_stride < 2 * (nsamp / R) || (out_stride & 1) != 0))
-        return fail(SDDC_ERR_ARG, "out_stride must be even and >= 2 nsamp / factor (got %zu, need %zu)", out_stride,
-                    2 * (nsamp / R));
-    if (!iq || !out) return fail(SDDC_ERR_ARG, "null buffer");
-    const uintptr_t sample = h->out_fmt == SDDC_DDC_FMT_CS16 ? 4 : 8;
-    if (((uintptr_t)iq & (sample - 1)) != 0) return fail(SDDC_ERR_ARG, "iq must be %d-byte aligned", (int)sample);
-    if (((uintptr_t)out & 7) != 0) return fail(SDDC_ERR_ARG, "the output must be 8-byte aligned");
-    return SDDC_OK;
+    return check_channel_io(h, "2 nsamp / factor", iq, nch, nsamp, in_stride, out, out_stride, nsamp / R);
 }
 
-// One launch on s: it reads the current tails and writes the other buffer, so it runs after every
-// earlier launch of the handle, whatever its stream; the buffers swap once it is enqueued.
 static int chdec_launch(sddc_ddc_t *h, const void *d_iq, int nch, size_t nsamp, size_t in_stride, float *d_out,
                         size_t out_stride, hipStream_t s)
 {
-    HIP_TRY(h->chdec_readers.order_before(s));
-    const int cur = h->chdec_cur;
-    const hipError_t e = sddc::launch_channel_decimate(h->tables, d_iq, h->out_fmt == SDDC_DDC_FMT_CS16, h->cs16_scale,
-                                                       nch, nsamp, in_stride, h->d_chdec_taps, (int)h->chdec_taps.size(),
-                                                       h->chdec_R, h->d_chdec_tail[cur], h->d_chdec_tail[cur ^ 1], d_out,
-                                                       out_stride, h->chdec_max_wgs, h->device, s);
-    const hipError_t er = h->chdec_readers.record(s);   // whatever was enqueued stays ordered
-    HIP_TRY(e);
-    h->chdec_cur = cur ^ 1;
-    HIP_TRY(er);
-    return SDDC_OK;
+    return h->chdec.launch(s, [&](const float2 *tail_in, float2 *tail_out) {
+        return sddc::launch_channel_decimate(h->tables, d_iq, h->out_fmt == SDDC_DDC_FMT_CS16, h->cs16_scale, nch, nsamp,
+                                             in_stride, h->chdec.d_taps, (int)h->chdec.taps.size(), h->chdec_R, tail_in,
+                                             tail_out, d_out, out_stride, h->chdec.max_wgs, h->device, s);
+    });
 }
 
 int sddc_ddc_channel_decimate_device(sddc_ddc_t *h, const void *d_iq, int nch, size_t nsamp, size_t in_stride,
@@ -1834,55 +1899,21 @@ int sddc_ddc_channel_decimate_host(sddc_ddc_t *h, const void *iq, int nch, size_
     if (!h) return fail(SDDC_ERR_ARG, "null handle");
     std::lock_guard<std::mutex> lk(h->mu);
     if (int rc = check_chdec_args(h, iq, nch, nsamp, in_stride, out, out_stride)) return rc;
-    const bool cs16 = h->out_fmt == SDDC_DDC_FMT_CS16;
-    const size_t nout = nsamp / (size_t)h->chdec_R;
     if (h->cpu) {
         try {
-            sddc::cpu::R2iq::channel_decimate(iq, cs16, (float)(1.0 / (double)h->cs16_scale), nch, nsamp,
-                                              nch > 1 ? in_stride : 0, h->chdec_taps.data(), (int)h->chdec_taps.size(),
-                                              h->chdec_R, h->chdec_tail_h.data(), out, nch > 1 ? out_stride : 0);
+            sddc::cpu::R2iq::channel_decimate(iq, h->out_fmt == SDDC_DDC_FMT_CS16, (float)(1.0 / (double)h->cs16_scale),
+                                              nch, nsamp, nch > 1 ? in_stride : 0, h->chdec.taps.data(),
+                                              (int)h->chdec.taps.size(), h->chdec_R, h->chdec.tail_h.data(), out,
+                                              nch > 1 ? out_stride : 0);
         } catch (const std::exception &ex) {   // thrown before any output or tail is written
             return fail(SDDC_ERR_NOMEM, "cpu backend: %s", ex.what());
         }
         return SDDC_OK;
     }
-    DeviceGuard g(h->device);
-    HIP_TRY(g.err);
-    // the spans that hold every channel's samples and outputs
-    const size_t in_bytes = ((size_t)(nch - 1) * (nch > 1 ? in_stride : 0) + 2 * nsamp) * (cs16 ? 2 : 4);
-    const size_t out_floats = (size_t)(nch - 1) * (nch > 1 ? out_stride : 0) + 2 * nout;
-    // the earlier host calls were synchronous: nothing reads the old buffers
-    if (in_bytes > h->chdec_in_cap) {
-        if (h->d_chdec_in) (void)hipFree(h->d_chdec_in);
-        h->d_chdec_in = nullptr;
-        h->chdec_in_cap = 0;
-        if (hipMalloc(&h->d_chdec_in, in_bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(SDDC_ERR_NOMEM, "channel_decimate_host: no device memory for %zu input bytes", in_bytes);
-        }
-        h->chdec_in_cap = in_bytes;
-    }
-    if (out_floats > h->chdec_out_cap) {
-        if (h->d_chdec_out) (void)hipFree(h->d_chdec_out);
-        h->d_chdec_out = nullptr;
-        h->chdec_out_cap = 0;
-        if (hipMalloc(&h->d_chdec_out, out_floats * sizeof(float)) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(SDDC_ERR_NOMEM, "channel_decimate_host: no device memory for %zu output floats", out_floats);
-        }
-        h->chdec_out_cap = out_floats;
-    }
-    HIP_TRY(hipMemcpyAsync(h->d_chdec_in, iq, in_bytes, hipMemcpyHostToDevice, h->stream));
-    const int rc = chdec_launch(h, h->d_chdec_in, nch, nsamp, in_stride, h->d_chdec_out, out_stride, h->stream);
-    if (rc == SDDC_OK) {   // the streams alone: the caller's memory between them stays as it is
-        if (nch == 1 || out_stride == 2 * nout)
-            HIP_TRY(hipMemcpyAsync(out, h->d_chdec_out, out_floats * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-        else
-            HIP_TRY(hipMemcpy2DAsync(out, out_stride * sizeof(float), h->d_chdec_out, out_stride * sizeof(float),
-                                     2 * nout * sizeof(float), (size_t)nch, hipMemcpyDeviceToHost, h->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(h->stream));   // also after a failed launch: the caller's input is free again
-    return rc;
+    return channel_host_roundtrip(h, h->chdec, "channel_decimate_host", iq, nch, nsamp, in_stride, out, out_stride,
+                                  nsamp / (size_t)h->chdec_R, [&](const void *d_in, float *d_out) {
+                                      return chdec_launch(h, d_in, nch, nsamp, in_stride, d_out, out_stride, h->stream);
+                                  });
 }
 
 /* ---- channel resampler: a streaming rational L/M polyphase FIR on the DDC's IQ output ------ */
@@ -1927,19 +1958,6 @@ static int chres_advance(int up, int down, int e, size_t nsamp, size_t nout)
     return (int)((int64_t)e + (int64_t)nout * down - (int64_t)nsamp * up);
 }
 
-// off: no taps, no tails (the caller holds h->mu and has waited for the launches in flight)
-static void chres_clear(sddc_ddc_t *h)
-{
-    h->chres_taps.clear();
-    h->chres_L = h->chres_M = h->chres_K = h->chres_nch = h->chres_e = 0;
-    h->chres_tail_h.clear();
-    for (float2 *&p : h->d_chres_tail) {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    }
-    h->chres_cur = 0;
-}
-
 /* internal (sddc_ddc_internal.h): the kernel's tile of (up, down, ntaps, format) */
 int sddc_ddc_internal_chres_layout(int up, int down, int ntaps, int cs16, int *tile_outputs, int *pitch,
                                    int *store_conflicts)
@@ -1959,7 +1977,7 @@ int sddc_ddc_internal_chres_set_position(sddc_ddc_t *h, uint64_t pos)
 {
     if (!h) return fail(SDDC_ERR_ARG, "null handle");
     std::lock_guard<std::mutex> lk(h->mu);
-    if (h->chres_taps.empty()) return fail(SDDC_ERR_STATE, "chres set position: no resampler set");
+    if (h->chres.taps.empty()) return fail(SDDC_ERR_STATE, "chres set position: no resampler set");
     h->chres_e = chres_position(h->chres_L, h->chres_M, pos);   // host state: a launch in flight has its own copy
     return SDDC_OK;
 }
@@ -1969,6 +1987,7 @@ int sddc_ddc_set_channel_resampler(sddc_ddc_t *h, const float *taps, int ntaps, 
     if (!h) return fail(SDDC_ERR_ARG, "null handle");
     const bool off = !taps || ntaps == 0;
     int K = 0;
+    float ordered[SDDC_DDC_RESAMPLE_MAX_TAPS + SDDC_DDC_RESAMPLE_MAX_UP];   // the kernel's order: up K < ntaps + up
     if (!off) {
         if (ntaps < 1 || ntaps > SDDC_DDC_RESAMPLE_MAX_TAPS)
             return fail(SDDC_ERR_ARG, "channel resampler: ntaps %d outside 1..%d", ntaps, SDDC_DDC_RESAMPLE_MAX_TAPS);
@@ -1983,61 +2002,14 @@ int sddc_ddc_set_channel_resampler(sddc_ddc_t *h, const float *taps, int ntaps, 
             return fail(SDDC_ERR_ARG, "channel resampler: nch %d outside 1..%d", nch, SDDC_DDC_MAX_CHANNELS);
         for (int j = 0; j < ntaps; j++)
             if (!std::isfinite(taps[j])) return fail(SDDC_ERR_ARG, "channel resampler: tap %d is not finite", j);
+        sddc::channel_resample_order_taps(taps, ntaps, up, ordered);
     }
     std::lock_guard<std::mutex> lk(h->mu);
-    const size_t tail = off ? 0 : (size_t)nch * (size_t)(K - 1);   // complex values
-    if (h->cpu) {
-        chres_clear(h);
-        if (off) return SDDC_OK;
-        try {
-            h->chres_tail_h.assign(2 * tail, 0.f);
-            h->chres_taps.assign(taps, taps + ntaps);
-        } catch (const std::exception &ex) {
-            chres_clear(h);
-            return fail(SDDC_ERR_NOMEM, "channel resampler: %s", ex.what());
-        }
-        h->chres_L = up;
-        h->chres_M = down;
-        h->chres_K = K;
-        h->chres_nch = nch;
-        return SDDC_OK;
-    }
-    DeviceGuard g(h->device);
-    HIP_TRY(g.err);
-    HIP_TRY(h->chres_readers.sync());   // earlier launches, on any stream, may still use the taps and the tails
-    chres_clear(h);                     // a failed upload leaves the resampler off
-    if (off) return SDDC_OK;
-    constexpr size_t kOrdered = SDDC_DDC_RESAMPLE_MAX_TAPS + SDDC_DDC_RESAMPLE_MAX_UP;   // up K < ntaps + up
-    if (!h->d_chres_taps) HIP_TRY(hipMalloc(&h->d_chres_taps, kOrdered * sizeof(float)));
-    try {   // the device copy is in the kernel's order
-        std::vector<float> ordered((size_t)up * (size_t)K);
-        sddc::channel_resample_order_taps(taps, ntaps, up, ordered.data());
-        HIP_TRY(hipMemcpy(h->d_chres_taps, ordered.data(), ordered.size() * sizeof(float), hipMemcpyHostToDevice));
-    } catch (const std::exception &ex) {
-        return fail(SDDC_ERR_NOMEM, "channel resampler: %s", ex.what());
-    }
-    if (tail) {
-        for (float2 *&p : h->d_chres_tail) {
-            if (hipMalloc(&p, tail * sizeof(float2)) != hipSuccess) {
-                (void)hipGetLastError();
-                p = nullptr;
-                chres_clear(h);
-                return fail(SDDC_ERR_NOMEM, "channel resampler: no device memory for %zu tail values", tail);
-            }
-        }
-        // zeroed on the handle's stream and waited for: the first launch may be on any stream
-        hipError_t e = hipMemsetAsync(h->d_chres_tail[0], 0, tail * sizeof(float2), h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) {
-            chres_clear(h);
-            HIP_TRY(e);
-        }
-    }
-    h->chres_taps.assign(taps, taps + ntaps);
-    h->chres_L = up;
-    h->chres_M = down;
-    h->chres_K = K;
-    h->chres_nch = nch;
+    if (int rc = h->chres.configure(h, "channel resampler", taps, ntaps, ordered, (size_t)up * (size_t)K, K - 1, nch))
+        return rc;
+    h->chres_L = off ? 0 : up;
+    h->chres_M = off ? 0 : down;
+    h->chres_e = 0;
     return SDDC_OK;
 }
 
@@ -2045,20 +2017,8 @@ int sddc_ddc_channel_resampler_reset(sddc_ddc_t *h)
 {
     if (!h) return fail(SDDC_ERR_ARG, "null handle");
     std::lock_guard<std::mutex> lk(h->mu);
-    if (h->chres_taps.empty()) return fail(SDDC_ERR_STATE, "channel resampler reset: no resampler set");
-    if (h->cpu) {
-        std::fill(h->chres_tail_h.begin(), h->chres_tail_h.end(), 0.f);
-        h->chres_e = 0;
-        return SDDC_OK;
-    }
-    const size_t tail = (size_t)h->chres_nch * (size_t)(h->chres_K - 1);
-    if (tail) {
-        DeviceGuard g(h->device);
-        HIP_TRY(g.err);
-        HIP_TRY(h->chres_readers.sync());   // earlier launches, on any stream, may still use the tails
-        HIP_TRY(hipMemsetAsync(h->d_chres_tail[h->chres_cur], 0, tail * sizeof(float2), h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));   // the next launch may be on any stream
-    }
+    if (h->chres.taps.empty()) return fail(SDDC_ERR_STATE, "channel resampler reset: no resampler set");
+    if (int rc = h->chres.reset(h)) return rc;
     h->chres_e = 0;
     return SDDC_OK;
 }
@@ -2073,7 +2033,7 @@ size_t sddc_ddc_channel_resample_samples(sddc_ddc_t *h, size_t nsamp)
 {
     if (!h) return 0;
     std::lock_guard<std::mutex> lk(h->mu);
-    if (h->chres_taps.empty() || nsamp > ((size_t)1 << 40)) return 0;
+    if (h->chres.taps.empty() || nsamp > ((size_t)1 << 40)) return 0;
     return chres_count(h->chres_L, h->chres_M, h->chres_e, nsamp);
 }
 
@@ -2081,43 +2041,28 @@ size_t sddc_ddc_channel_resample_samples(sddc_ddc_t *h, size_t nsamp)
 static int check_chres_args(const sddc_ddc_t *h, const void *iq, int nch, size_t nsamp, size_t in_stride,
                             const float *out, size_t out_stride, size_t *nout)
 {
-    if (h->chres_taps.empty()) return fail(SDDC_ERR_STATE, "channel resample: no resampler set");
-    if (nch != h->chres_nch)
+    if (h->chres.taps.empty()) return fail(SDDC_ERR_STATE, "channel resample: no resampler set");
+    if (nch != h->chres.nch)
         return fail(SDDC_ERR_STATE, "channel resample: the resampler is set for %d channels, the call has %d",
-                    h->chres_nch, nch);
+                    h->chres.nch, nch);
     if (nsamp == 0 || nsamp > ((size_t)1 << 40))
         return fail(SDDC_ERR_ARG, "nsamp must be in 1..2^40 (got %zu)", nsamp);
-    const size_t n = chres_count(h->chres_L, h->chres_M, h->chres_e, nsamp);
-    if (nch > 1 && (in_stride < 2 * nsamp || (in_stride & 1) != 0))
-        return fail(SDDC_ERR_ARG, "in_stride must be even and >= 2 nsamp (got %zu, nsamp %zu)", in_stride, nsamp);
-    if (nch > 1 && (out_stride < 2 * n || (out_stride & 1) != 0))
-        return fail(SDDC_ERR_ARG, "out_stride must be even and >= 2 nout (got %zu, need %zu)", out_stride, 2 * n);
-    if (!iq || !out) return fail(SDDC_ERR_ARG, "null buffer");
-    const uintptr_t sample = h->out_fmt == SDDC_DDC_FMT_CS16 ? 4 : 8;
-    if (((uintptr_t)iq & (sample - 1)) != 0) return fail(SDDC_ERR_ARG, "iq must be %d-byte aligned", (int)sample);
-    if (((uintptr_t)out & 7) != 0) return fail(SDDC_ERR_ARG, "the output must be 8-byte aligned");
-    *nout = n;
-    return SDDC_OK;
+    *nout = chres_count(h->chres_L, h->chres_M, h->chres_e, nsamp);
+    return check_channel_io(h, "2 nout", iq, nch, nsamp, in_stride, out, out_stride, *nout);
 }
 
-// One launch on s: it reads the current tails and writes the other buffer, so it runs after every
-// earlier launch of the handle, whatever its stream; the buffers swap and the position advances
-// once it is enqueued.
+// the position advances once the launch is enqueued
 static int chres_launch(sddc_ddc_t *h, const void *d_iq, int nch, size_t nsamp, size_t in_stride, float *d_out,
                         size_t out_stride, size_t nout, hipStream_t s)
 {
-    HIP_TRY(h->chres_readers.order_before(s));
-    const int cur = h->chres_cur;
-    const hipError_t e = sddc::launch_channel_resample(
-        h->tables, d_iq, h->out_fmt == SDDC_DDC_FMT_CS16, h->cs16_scale, nch, nsamp, in_stride, h->d_chres_taps,
-        (int)h->chres_taps.size(), h->chres_L, h->chres_M, h->chres_e, nout, h->d_chres_tail[cur],
-        h->d_chres_tail[cur ^ 1], d_out, out_stride, h->chres_max_wgs, h->device, s);
-    const hipError_t er = h->chres_readers.record(s);   // whatever was enqueued stays ordered
-    HIP_TRY(e);
-    if (h->chres_K > 1) h->chres_cur = cur ^ 1;
-    h->chres_e = chres_advance(h->chres_L, h->chres_M, h->chres_e, nsamp, nout);
-    HIP_TRY(er);
-    return SDDC_OK;
+    return h->chres.launch(s, [&](const float2 *tail_in, float2 *tail_out) {
+        const hipError_t e = sddc::launch_channel_resample(
+            h->tables, d_iq, h->out_fmt == SDDC_DDC_FMT_CS16, h->cs16_scale, nch, nsamp, in_stride, h->chres.d_taps,
+            (int)h->chres.taps.size(), h->chres_L, h->chres_M, h->chres_e, nout, tail_in, tail_out, d_out, out_stride,
+            h->chres.max_wgs, h->device, s);
+        if (e == hipSuccess) h->chres_e = chres_advance(h->chres_L, h->chres_M, h->chres_e, nsamp, nout);
+        return e;
+    });
 }
 
 int sddc_ddc_channel_resample_device(sddc_ddc_t *h, const void *d_iq, int nch, size_t nsamp, size_t in_stride,
@@ -2142,13 +2087,12 @@ int sddc_ddc_channel_resample_host(sddc_ddc_t *h, const void *iq, int nch, size_
     std::lock_guard<std::mutex> lk(h->mu);
     size_t nout = 0;
     if (int rc = check_chres_args(h, iq, nch, nsamp, in_stride, out, out_stride, &nout)) return rc;
-    const bool cs16 = h->out_fmt == SDDC_DDC_FMT_CS16;
     if (h->cpu) {
         try {
-            sddc::cpu::R2iq::channel_resample(iq, cs16, (float)(1.0 / (double)h->cs16_scale), nch, nsamp,
-                                              nch > 1 ? in_stride : 0, h->chres_taps.data(), (int)h->chres_taps.size(),
-                                              h->chres_L, h->chres_M, h->chres_e, nout, h->chres_tail_h.data(), out,
-                                              nch > 1 ? out_stride : 0);
+            sddc::cpu::R2iq::channel_resample(iq, h->out_fmt == SDDC_DDC_FMT_CS16, (float)(1.0 / (double)h->cs16_scale),
+                                              nch, nsamp, nch > 1 ? in_stride : 0, h->chres.taps.data(),
+                                              (int)h->chres.taps.size(), h->chres_L, h->chres_M, h->chres_e, nout,
+                                              h->chres.tail_h.data(), out, nch > 1 ? out_stride : 0);
         } catch (const std::exception &ex) {   // thrown before any output or tail is written
             return fail(SDDC_ERR_NOMEM, "cpu backend: %s", ex.what());
         }
@@ -2156,43 +2100,11 @@ int sddc_ddc_channel_resample_host(sddc_ddc_t *h, const void *iq, int nch, size_
         if (nout_p) *nout_p = nout;
         return SDDC_OK;
     }
-    DeviceGuard g(h->device);
-    HIP_TRY(g.err);
-    // the spans that hold every channel's samples and outputs (one float2 at least: a call without an output)
-    const size_t in_bytes = ((size_t)(nch - 1) * (nch > 1 ? in_stride : 0) + 2 * nsamp) * (cs16 ? 2 : 4);
-    const size_t out_floats = (size_t)(nch - 1) * (nch > 1 ? out_stride : 0) + 2 * nout;
-    const size_t out_alloc = out_floats ? out_floats : 2;
-    // the earlier host calls were synchronous: nothing reads the old buffers
-    if (in_bytes > h->chres_in_cap) {
-        if (h->d_chres_in) (void)hipFree(h->d_chres_in);
-        h->d_chres_in = nullptr;
-        h->chres_in_cap = 0;
-        if (hipMalloc(&h->d_chres_in, in_bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(SDDC_ERR_NOMEM, "channel_resample_host: no device memory for %zu input bytes", in_bytes);
-        }
-        h->chres_in_cap = in_bytes;
-    }
-    if (out_alloc > h->chres_out_cap) {
-        if (h->d_chres_out) (void)hipFree(h->d_chres_out);
-        h->d_chres_out = nullptr;
-        h->chres_out_cap = 0;
-        if (hipMalloc(&h->d_chres_out, out_alloc * sizeof(float)) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(SDDC_ERR_NOMEM, "channel_resample_host: no device memory for %zu output floats", out_alloc);
-        }
-        h->chres_out_cap = out_alloc;
-    }
-    HIP_TRY(hipMemcpyAsync(h->d_chres_in, iq, in_bytes, hipMemcpyHostToDevice, h->stream));
-    const int rc = chres_launch(h, h->d_chres_in, nch, nsamp, in_stride, h->d_chres_out, out_stride, nout, h->stream);
-    if (rc == SDDC_OK && nout) {   // the streams alone: the caller's memory between them stays as it is
-        if (nch == 1 || out_stride == 2 * nout)
-            HIP_TRY(hipMemcpyAsync(out, h->d_chres_out, out_floats * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-        else
-            HIP_TRY(hipMemcpy2DAsync(out, out_stride * sizeof(float), h->d_chres_out, out_stride * sizeof(float),
-                                     2 * nout * sizeof(float), (size_t)nch, hipMemcpyDeviceToHost, h->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(h->stream));   // also after a failed launch: the caller's input is free again
+    const int rc = channel_host_roundtrip(h, h->chres, "channel_resample_host", iq, nch, nsamp, in_stride, out, out_stride,
+                                          nout, [&](const void *d_in, float *d_out) {
+                                              return chres_launch(h, d_in, nch, nsamp, in_stride, d_out, out_stride, nout,
+                                                                  h->stream);
+                                          });
     if (rc == SDDC_OK && nout_p) *nout_p = nout;
     return rc;
 }

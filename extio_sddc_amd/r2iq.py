@@ -344,6 +344,39 @@ class R2iq:
                                                _stream_handle(stream)))
 
 
+    # -- the channel stages' argument checks (spectrum, decimator, resampler) ------
+    def _channel_host_array(self, iq):
+        """(iq, nch, nsamp) of a channel stage's host input: contiguous, with the channel axis, in
+        the handle's output format."""
+        iq = np.asarray(iq)
+        if self._fmt == FMT_CS16:
+            if iq.dtype != np.int16 or iq.ndim not in (2, 3) or iq.shape[-1] != 2:
+                raise DDCError(-1, "CS16 handle: iq must be int16 [nch, nsamp, 2]")
+            iq = np.ascontiguousarray(iq.reshape((1,) + iq.shape if iq.ndim == 2 else iq.shape))
+        else:
+            if iq.dtype != np.complex64 or iq.ndim not in (1, 2):
+                raise DDCError(-1, "CF32 handle: iq must be complex64 [nch, nsamp]")
+            iq = np.ascontiguousarray(iq.reshape(1, -1) if iq.ndim == 1 else iq)
+        return iq, iq.shape[0], iq.shape[1]
+
+    def _check_channel_device(self, d_iq, d_out, nch, nsamp, in_stride, nout, out_stride):
+        """The tensors of a stream stage's device call: on the device, of the handle's format,
+        contiguous, and large enough for nch channels of nsamp samples in and nout out."""
+        import torch
+        if not (d_iq.is_cuda and d_out.is_cuda):
+            raise DDCError(-1, "device path needs device tensors")
+        want = torch.int16 if self._fmt == FMT_CS16 else torch.float32
+        if d_iq.dtype != want or d_out.dtype != torch.float32:
+            raise DDCError(-1, f"d_iq must be {want} and d_out float32")
+        if not (d_iq.is_contiguous() and d_out.is_contiguous()):
+            raise DDCError(-1, "tensors must be contiguous")
+        need = (nch - 1) * in_stride + 2 * nsamp
+        if d_iq.numel() < need:
+            raise DDCError(-1, f"d_iq has {d_iq.numel()} components, need {need}")
+        need = (nch - 1) * out_stride + 2 * nout
+        if d_out.numel() < need:
+            raise DDCError(-1, f"d_out has {d_out.numel()} floats, need {need}")
+
     # -- channel spectrum ------------------------------------------------------
     def setChannelSpectrumWindow(self, w) -> None:
         """The channel spectrum's window (see window); its length, one of CHANNEL_SPECTRUM_SIZES, is
@@ -361,16 +394,7 @@ class R2iq:
         stream may drop the channel axis.  Frame f of row r is the n samples at
         (r * frames_per_row + f) * hop (hop defaults to n / 2), nrows defaults to all whole rows.
         Returns float32 [nch, nrows, n], q = n / 2 the channel's centre, ascending in frequency."""
-        iq = np.asarray(iq)
-        if self._fmt == FMT_CS16:
-            if iq.dtype != np.int16 or iq.ndim not in (2, 3) or iq.shape[-1] != 2:
-                raise DDCError(-1, "CS16 handle: iq must be int16 [nch, nsamp, 2]")
-            iq = np.ascontiguousarray(iq.reshape((1,) + iq.shape if iq.ndim == 2 else iq.shape))
-        else:
-            if iq.dtype != np.complex64 or iq.ndim not in (1, 2):
-                raise DDCError(-1, "CF32 handle: iq must be complex64 [nch, nsamp]")
-            iq = np.ascontiguousarray(iq.reshape(1, -1) if iq.ndim == 1 else iq)
-        nch, nsamp = iq.shape[0], iq.shape[1]
+        iq, nch, nsamp = self._channel_host_array(iq)
         hop = n // 2 if hop is None else int(hop)
         if hop < 1 or frames_per_row < 1 or nsamp < n:
             raise DDCError(-1, f"hop {hop}, frames_per_row {frames_per_row} must be >= 1 and nsamp {nsamp} >= n {n}")
@@ -433,16 +457,7 @@ class R2iq:
         channel's last ntaps - 1 samples for the next call."""
         if self._decim is None:
             raise DDCError(-4, "no channel decimator set")
-        iq = np.asarray(iq)
-        if self._fmt == FMT_CS16:
-            if iq.dtype != np.int16 or iq.ndim not in (2, 3) or iq.shape[-1] != 2:
-                raise DDCError(-1, "CS16 handle: iq must be int16 [nch, nsamp, 2]")
-            iq = np.ascontiguousarray(iq.reshape((1,) + iq.shape if iq.ndim == 2 else iq.shape))
-        else:
-            if iq.dtype != np.complex64 or iq.ndim not in (1, 2):
-                raise DDCError(-1, "CF32 handle: iq must be complex64 [nch, nsamp]")
-            iq = np.ascontiguousarray(iq.reshape(1, -1) if iq.ndim == 1 else iq)
-        nch, nsamp = iq.shape[0], iq.shape[1]
+        iq, nch, nsamp = self._channel_host_array(iq)
         nout = channel_decimate_samples(self._decim[1], nsamp)
         if nout == 0:
             raise DDCError(-1, f"nsamp {nsamp} must be a positive multiple of the factor {self._decim[1]}")
@@ -457,25 +472,12 @@ class R2iq:
         float32 (CS16: int16) device tensor, channel c at c * in_stride components, nsamp complex
         samples each; d_out float32, channel c's nsamp / factor (I, Q) pairs at c * out_stride
         floats.  Enqueued on `stream` like process_device; the calls of one handle run in call order."""
-        import torch
         if self._decim is None:
             raise DDCError(-4, "no channel decimator set")
-        if not (d_iq.is_cuda and d_out.is_cuda):
-            raise DDCError(-1, "device path needs device tensors")
-        want = torch.int16 if self._fmt == FMT_CS16 else torch.float32
-        if d_iq.dtype != want or d_out.dtype != torch.float32:
-            raise DDCError(-1, f"d_iq must be {want} and d_out float32")
-        if not (d_iq.is_contiguous() and d_out.is_contiguous()):
-            raise DDCError(-1, "tensors must be contiguous")
         nout = channel_decimate_samples(self._decim[1], nsamp)
         if nch < 1 or nout == 0:
             raise DDCError(-1, f"nch must be >= 1 and nsamp {nsamp} a positive multiple of the factor {self._decim[1]}")
-        need = (nch - 1) * in_stride + 2 * nsamp
-        if d_iq.numel() < need:
-            raise DDCError(-1, f"d_iq has {d_iq.numel()} components, need {need}")
-        need = (nch - 1) * out_stride + 2 * nout
-        if d_out.numel() < need:
-            raise DDCError(-1, f"d_out has {d_out.numel()} floats, need {need}")
+        self._check_channel_device(d_iq, d_out, nch, nsamp, in_stride, nout, out_stride)
         check(self._L.sddc_ddc_channel_decimate_device(self._h, d_iq.data_ptr(), nch, nsamp, in_stride,
                                                        d_out.data_ptr(), out_stride, _stream_handle(stream)))
 
@@ -512,16 +514,7 @@ class R2iq:
         ceil(ntaps / up) - 1 samples and the position for the next call."""
         if self._resamp is None:
             raise DDCError(-4, "no channel resampler set")
-        iq = np.asarray(iq)
-        if self._fmt == FMT_CS16:
-            if iq.dtype != np.int16 or iq.ndim not in (2, 3) or iq.shape[-1] != 2:
-                raise DDCError(-1, "CS16 handle: iq must be int16 [nch, nsamp, 2]")
-            iq = np.ascontiguousarray(iq.reshape((1,) + iq.shape if iq.ndim == 2 else iq.shape))
-        else:
-            if iq.dtype != np.complex64 or iq.ndim not in (1, 2):
-                raise DDCError(-1, "CF32 handle: iq must be complex64 [nch, nsamp]")
-            iq = np.ascontiguousarray(iq.reshape(1, -1) if iq.ndim == 1 else iq)
-        nch, nsamp = iq.shape[0], iq.shape[1]
+        iq, nch, nsamp = self._channel_host_array(iq)
         if nsamp < 1:
             raise DDCError(-1, "nsamp must be >= 1")
         nout = self.channel_resample_samples(nsamp)
@@ -538,25 +531,12 @@ class R2iq:
         samples each; d_out float32, channel c's nout (I, Q) pairs at c * out_stride floats.  Returns
         nout = channel_resample_samples(nsamp) at the call (possibly 0).  Enqueued on `stream` like
         process_device; the calls of one handle run in call order."""
-        import torch
         if self._resamp is None:
             raise DDCError(-4, "no channel resampler set")
-        if not (d_iq.is_cuda and d_out.is_cuda):
-            raise DDCError(-1, "device path needs device tensors")
-        want = torch.int16 if self._fmt == FMT_CS16 else torch.float32
-        if d_iq.dtype != want or d_out.dtype != torch.float32:
-            raise DDCError(-1, f"d_iq must be {want} and d_out float32")
-        if not (d_iq.is_contiguous() and d_out.is_contiguous()):
-            raise DDCError(-1, "tensors must be contiguous")
         if nch < 1 or nsamp < 1:
             raise DDCError(-1, "nch and nsamp must be >= 1")
         nout = self.channel_resample_samples(nsamp)
-        need = (nch - 1) * in_stride + 2 * nsamp
-        if d_iq.numel() < need:
-            raise DDCError(-1, f"d_iq has {d_iq.numel()} components, need {need}")
-        need = (nch - 1) * out_stride + 2 * nout
-        if d_out.numel() < need:
-            raise DDCError(-1, f"d_out has {d_out.numel()} floats, need {need}")
+        self._check_channel_device(d_iq, d_out, nch, nsamp, in_stride, nout, out_stride)
         got = ctypes.c_size_t(0)
         check(self._L.sddc_ddc_channel_resample_device(self._h, d_iq.data_ptr(), nch, nsamp, in_stride,
                                                        d_out.data_ptr(), out_stride, ctypes.addressof(got),

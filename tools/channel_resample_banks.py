@@ -21,17 +21,13 @@ layout() restates channel_resample_layout (K, the tile's values of a and the pit
 picks: the one in [columns needed, + 15] that the LDS holds with the fewest extra store cycles);
 tests/test_channel_resample_cpu.py holds the two against each other.
 """
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from channel_decimate_banks import store_conflicts  # noqa: E402,F401  the shared stage's stores (channel_stage.hpp)
+
 LDS, MAXA, PAD = 8128, 512, 15   # ddc_kernels.h kChResLds, kChResMaxA, kChResPitchPad
-
-
-def store_conflicts(M, pitch, V):
-    tot = 0
-    for e in range(V):
-        slots = [((V * l + e) % M) * pitch + (V * l + e) // M for l in range(64)]
-        for g0 in range(0, 64, 16):
-            ks = [s % 16 for s in slots[g0:g0 + 16]]
-            tot += max(ks.count(k) for k in set(ks)) - 1
-    return tot
 
 
 def read_conflicts(M, pitch, K, transposed=True):
