@@ -72,6 +72,11 @@ SIGNATURES = {
     "sddc_ddc_channel_resample_samples": (_SZ, [_P, _SZ]),
     "sddc_ddc_channel_resample_device": (_I, [_P, _P, _I, _SZ, _SZ, _P, _SZ, _P, _P]),
     "sddc_ddc_channel_resample_host": (_I, [_P, _P, _I, _SZ, _SZ, _P, _SZ, _P]),
+    "sddc_ddc_bfo_word": (ctypes.c_uint32, [ctypes.c_double]),
+    "sddc_ddc_set_channel_demodulator": (_I, [_P, _P, _P, _P, _I, _I]),
+    "sddc_ddc_channel_demodulator_reset": (_I, [_P]),
+    "sddc_ddc_channel_demodulate_device": (_I, [_P, _P, _I, _SZ, _SZ, _P, _SZ, _P, _P]),
+    "sddc_ddc_channel_demodulate_host": (_I, [_P, _P, _I, _SZ, _SZ, _P, _SZ, _P]),
     "sddc_ddc_register_host": (_I, [_P, _P, _SZ]),
     "sddc_ddc_unregister_host": (_I, [_P, _P]),
     # include/sddc_fft.h

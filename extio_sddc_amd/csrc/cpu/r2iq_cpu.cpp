@@ -439,5 +439,48 @@ void R2iq::channel_resample(const void *iq, bool cs16, float inv_s, int nch, siz
     }
 }
 
+// The channel demodulator: demod_math.h's formulas sample by sample; the previous sample of the
+// call's first one is the kept value, and the call's last sample value is kept for the next call.
+void R2iq::channel_demodulate(const void *iq, bool cs16, float inv_s, int nch, size_t nsamp, size_t in_stride,
+                              const ChDemChannel *chan, uint32_t pos, float *last, void *out, bool s16,
+                              size_t out_stride, float *power)
+{
+    for (int c = 0; c < nch; c++) {
+        const char *x = static_cast<const char *>(iq) + (size_t)c * in_stride * (cs16 ? 2 : 4);
+        const int16_t *xs = reinterpret_cast<const int16_t *>(x);
+        const float *xf = reinterpret_cast<const float *>(x);
+        float *yf = static_cast<float *>(out) + (size_t)c * out_stride;
+        int16_t *ys = static_cast<int16_t *>(out) + (size_t)c * out_stride;
+        const ChDemChannel ch = chan[c];
+        float Ip = last[2 * c], Qp = last[2 * c + 1], acc = 0.f;
+        for (size_t i = 0; i < nsamp; i++) {
+            const float I = cs16 ? (float)xs[2 * i] * inv_s : xf[2 * i];
+            const float Q = cs16 ? (float)xs[2 * i + 1] * inv_s : xf[2 * i + 1];
+            float y;
+            if (ch.mode == 0) y = demod::demod_am(I, Q, ch.gain);
+            else if (ch.mode == 1) y = demod::demod_fm(I, Q, Ip, Qp, ch.gain);
+            else y = demod::demod_bfo(I, Q, ch.word * (pos + (uint32_t)i), ch.gain);
+            if (s16) ys[i] = demod::demod_s16(y);
+            else yf[i] = y;
+            if (power) acc += demod::demod_power(I, Q);
+            Ip = I;
+            Qp = Q;
+        }
+        last[2 * c] = Ip;
+        last[2 * c + 1] = Qp;
+        if (power) power[c] = acc * (float)(1.0 / (double)nsamp);
+    }
+}
+
+void R2iq::demod_angle_n(const float *im, const float *re, size_t n, float *out)
+{
+    for (size_t i = 0; i < n; i++) out[i] = demod::demod_angle(im[i], re[i]);
+}
+
+void R2iq::demod_sincos_n(const uint32_t *words, size_t n, float *c, float *s)
+{
+    for (size_t i = 0; i < n; i++) demod::demod_sincos_word(words[i], c + i, s + i);
+}
+
 }  // namespace cpu
 }  // namespace sddc

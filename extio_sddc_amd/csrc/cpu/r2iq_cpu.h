@@ -23,6 +23,7 @@
 #include <memory>
 #include <vector>
 
+#include "../demod_math.h"
 #include "fft_avx2.hpp"
 
 namespace sddc {
@@ -82,6 +83,18 @@ public:
     static void channel_resample(const void *iq, bool cs16, float inv_s, int nch, size_t nsamp, size_t in_stride,
                                  const float *taps, int ntaps, int L, int M, int e, size_t nout, float *tail, float *out,
                                  size_t out_stride);
+    // The channel demodulator (sddc_ddc.h, sddc_ddc_channel_demodulate_host; demod_math.h): channel c's
+    // nsamp samples demodulated by chan[c] (mode, gain, BFO word) at stream position pos, streams and
+    // formats as for channel_decimate; channel c's outputs (float, or int16 when s16) at out + c *
+    // out_stride samples.  last: [nch][2] floats, each channel's last sample value before the call,
+    // replaced by the one after it.  power: null, or [nch] floats that receive the mean of
+    // fmaf(I, I, Q Q) over the call, summed sample by sample.  Stateless otherwise.
+    static void channel_demodulate(const void *iq, bool cs16, float inv_s, int nch, size_t nsamp, size_t in_stride,
+                                   const ChDemChannel *chan, uint32_t pos, float *last, void *out, bool s16,
+                                   size_t out_stride, float *power);
+    // demod_math.h's routines on arrays (the accuracy sweeps of tests/test_channel_demod_cpu.py)
+    static void demod_angle_n(const float *im, const float *re, size_t n, float *out);
+    static void demod_sincos_n(const uint32_t *words, size_t n, float *c, float *s);
 
 private:
     struct Buf;

@@ -249,6 +249,23 @@ hipError_t launch_channel_resample(const KernelTables &t, const void *d_iq, int 
                                    int e, size_t nout, const float2 *d_tail_in, float2 *d_tail_out, float *d_out,
                                    size_t out_stride, int max_wgs, int device, hipStream_t s);
 
+// Channel demodulator (ddc_channel_demod.hip, sddc_ddc_channel_demodulate_device): AM / FM / BFO audio
+// (demod_math.h) from nch streams laid out as for the decimator, any nsamp >= 1.  d_chan: [nch] mode,
+// gain and BFO word; pos: the stream position of the call's first sample mod 2^32.  d_last_in /
+// d_last_out: [nch] float2, each channel's last sample value before / after this call (two buffers).
+// d_out: float (s16 = 0) or int16 (s16 = 1) samples, channel c at c * out_stride samples, aligned to
+// one sample.  d_power: [nch] floats or nullptr; with it d_partial holds nch * channel_demod_tiles(nsamp)
+// floats, the tile sums that a second launch adds per channel in a fixed order.  One work item per
+// (channel, tile of kChDemTile samples); max_wgs > 0 caps the grid (tests).  The caller has checked
+// the strides.
+struct ChDemChannel;                   // demod_math.h: a channel's mode, gain and BFO word
+constexpr int kChDemTile = 2048;       // samples per tile: 4 (CF32) or 2 (CS16) 16-byte loads per thread
+inline size_t channel_demod_tiles(size_t nsamp) { return (nsamp + kChDemTile - 1) / kChDemTile; }
+hipError_t launch_channel_demod(const KernelTables &t, const void *d_iq, int cs16, float cs16_scale, int nch,
+                                size_t nsamp, size_t in_stride, const ChDemChannel *d_chan, uint32_t pos,
+                                const float2 *d_last_in, float2 *d_last_out, void *d_out, int s16, size_t out_stride,
+                                float *d_power, float *d_partial, int max_wgs, int device, hipStream_t s);
+
 // batched FFTs (fft_batch.hip, include/sddc_fft.h); fft_prepare fills the device's twiddle
 // table once (synchronises s the first time)
 hipError_t fft_prepare(hipStream_t s);

@@ -206,6 +206,56 @@ struct ChannelStream {
     }
 };
 
+// The state of the channel demodulator (sddc_ddc_channel_demodulate_*): each channel's mode, gain and
+// BFO word (empty = off) with their device copy, the output format, the stream position mod 2^32
+// (host) and each channel's last sample value as float2 in two device buffers that swap per launch,
+// as ChannelStream's tails do.  d_partial holds the power's tile sums of one call (grown on demand,
+// after a wait for the launches that may still use it).  A CPU handle keeps the last samples in
+// last_h.  d_in / d_out / d_pow are the host call's device buffers.  All under the handle's mu.
+struct ChannelDemod {
+    std::vector<sddc::ChDemChannel> chan;
+    int nch = 0, out_fmt = 0;
+    uint32_t pos = 0;
+    sddc::ChDemChannel *d_chan = nullptr;
+    float2 *d_last[2] = {};                // [nch] each
+    int cur = 0;
+    std::vector<float> last_h;             // CPU handle: [nch][2]
+    float *d_partial = nullptr;
+    size_t partial_cap = 0;                // floats
+    Readers readers;
+    int max_wgs = 0;
+    void *d_in = nullptr, *d_out = nullptr;
+    float *d_pow = nullptr;
+    size_t in_cap = 0, out_cap = 0, pow_cap = 0;   // bytes, bytes, floats
+
+    void clear()
+    {
+        chan.clear();
+        nch = out_fmt = 0;
+        pos = 0;
+        last_h.clear();
+        if (d_chan) (void)hipFree(d_chan);
+        d_chan = nullptr;
+        for (float2 *&p : d_last) {
+            if (p) (void)hipFree(p);
+            p = nullptr;
+        }
+        cur = 0;
+    }
+    void free_all()
+    {
+        clear();
+        if (d_partial) (void)hipFree(d_partial);
+        if (d_in) (void)hipFree(d_in);
+        if (d_out) (void)hipFree(d_out);
+        if (d_pow) (void)hipFree(d_pow);
+        d_partial = d_pow = nullptr;
+        d_in = d_out = nullptr;
+        partial_cap = in_cap = out_cap = pow_cap = 0;
+        readers.clear();
+    }
+};
+
 }  // namespace
 
 struct sddc_ddc {
@@ -374,6 +424,7 @@ struct sddc_ddc {
     ChannelStream chdec, chres;            // max_wgs: SDDC_DDC_PARAM_CH{DEC,RES}_MAX_WGS
     int chdec_R = 0;
     int chres_L = 0, chres_M = 0, chres_e = 0;
+    ChannelDemod chdem;                    // max_wgs: SDDC_DDC_PARAM_CHDEM_MAX_WGS
 
     // CPU handle (device SDDC_DDC_DEVICE_CPU): the AVX2 backend; no HIP object above exists
     std::unique_ptr<sddc::cpu::R2iq> cpu;
@@ -725,6 +776,7 @@ int sddc_ddc_destroy(sddc_ddc_t *h)
         (void)h->chsp_readers.sync();
         (void)h->chdec.readers.sync();
         (void)h->chres.readers.sync();
+        (void)h->chdem.readers.sync();
         if (h->d_tables) (void)hipFree(h->d_tables);
         for (auto &sl : h->hs) {
             if (sl.d_in) (void)hipFree(sl.d_in);
@@ -758,6 +810,7 @@ int sddc_ddc_destroy(sddc_ddc_t *h)
         h->chsp_readers.clear();
         h->chdec.free_all();
         h->chres.free_all();
+        h->chdem.free_all();
         if (h->fsa.h_ring) (void)hipHostFree(h->fsa.h_ring);   // its writers were waited for above
         h->readers.clear();
         h->ch_readers.clear();
@@ -1279,6 +1332,10 @@ int sddc_ddc_internal_set_param(sddc_ddc_t *h, int param, int value)
     case SDDC_DDC_PARAM_CHRES_MAX_WGS:
         if (value < 0) return fail(SDDC_ERR_ARG, "channel resampler workgroup cap %d is negative", value);
         h->chres.max_wgs = value;
+        return SDDC_OK;
+    case SDDC_DDC_PARAM_CHDEM_MAX_WGS:
+        if (value < 0) return fail(SDDC_ERR_ARG, "channel demodulator workgroup cap %d is negative", value);
+        h->chdem.max_wgs = value;
         return SDDC_OK;
     default:
         return fail(SDDC_ERR_ARG, "unknown parameter %d", param);
@@ -2106,6 +2163,224 @@ int sddc_ddc_channel_resample_host(sddc_ddc_t *h, const void *iq, int nch, size_
                                                                   h->stream);
                                           });
     if (rc == SDDC_OK && nout_p) *nout_p = nout;
+    return rc;
+}
+
+/* ---- channel demodulator: streaming AM / FM / BFO audio from the channel streams ---------- */
+uint32_t sddc_ddc_bfo_word(double relative_freq)
+{
+    if (!std::isfinite(relative_freq)) return 0u;
+    const double r = relative_freq - std::floor(relative_freq + 0.5);   // [-0.5, 0.5)
+    return (uint32_t)(int64_t)std::llround(r * 4294967296.0);
+}
+
+/* internal (sddc_ddc_internal.h): demod_math.h's two routines as the CPU backend compiles them */
+int sddc_ddc_internal_demod_angle(const float *im, const float *re, size_t n, float *out)
+{
+    if (!im || !re || !out) return fail(SDDC_ERR_ARG, "demod angle: null pointer");
+    sddc::cpu::R2iq::demod_angle_n(im, re, n, out);
+    return SDDC_OK;
+}
+
+int sddc_ddc_internal_demod_sincos(const uint32_t *words, size_t n, float *c, float *s)
+{
+    if (!words || !c || !s) return fail(SDDC_ERR_ARG, "demod sincos: null pointer");
+    sddc::cpu::R2iq::demod_sincos_n(words, n, c, s);
+    return SDDC_OK;
+}
+
+/* internal: the stream position, the last samples left as they are */
+int sddc_ddc_internal_chdem_set_position(sddc_ddc_t *h, uint32_t pos)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->chdem.chan.empty()) return fail(SDDC_ERR_STATE, "chdem set position: no demodulator set");
+    h->chdem.pos = pos;   // host state: a launch in flight has its own copy
+    return SDDC_OK;
+}
+
+int sddc_ddc_set_channel_demodulator(sddc_ddc_t *h, const int *modes, const float *gains, const uint32_t *bfo_words,
+                                     int nch, int out_format)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    const bool off = !modes || nch == 0;
+    std::vector<sddc::ChDemChannel> chan;
+    if (!off) {
+        if (nch < 1 || nch > SDDC_DDC_MAX_CHANNELS)
+            return fail(SDDC_ERR_ARG, "channel demodulator: nch %d outside 1..%d", nch, SDDC_DDC_MAX_CHANNELS);
+        if (out_format != SDDC_DDC_AUDIO_F32 && out_format != SDDC_DDC_AUDIO_S16)
+            return fail(SDDC_ERR_ARG, "channel demodulator: unknown output format %d", out_format);
+        try {
+            chan.resize((size_t)nch);
+        } catch (const std::exception &ex) {
+            return fail(SDDC_ERR_NOMEM, "channel demodulator: %s", ex.what());
+        }
+        for (int c = 0; c < nch; c++) {
+            if (modes[c] < SDDC_DDC_DEMOD_AM || modes[c] > SDDC_DDC_DEMOD_BFO)
+                return fail(SDDC_ERR_ARG, "channel demodulator: mode %d of channel %d outside 0..2", modes[c], c);
+            const float g = gains ? gains[c] : 1.f;
+            if (!std::isfinite(g)) return fail(SDDC_ERR_ARG, "channel demodulator: the gain of channel %d is not finite", c);
+            chan[(size_t)c] = sddc::ChDemChannel{modes[c], g, bfo_words ? bfo_words[c] : 0u, 0u};
+        }
+    }
+    std::lock_guard<std::mutex> lk(h->mu);
+    ChannelDemod &st = h->chdem;
+    if (h->cpu) {
+        st.clear();
+        if (off) return SDDC_OK;
+        try {
+            st.last_h.assign(2 * (size_t)nch, 0.f);
+        } catch (const std::exception &ex) {
+            st.clear();
+            return fail(SDDC_ERR_NOMEM, "channel demodulator: %s", ex.what());
+        }
+    } else {
+        DeviceGuard g(h->device);
+        HIP_TRY(g.err);
+        HIP_TRY(st.readers.sync());   // earlier launches, on any stream, may still use the state
+        st.clear();                   // a failed upload leaves the demodulator off
+        if (off) return SDDC_OK;
+        hipError_t e = hipMalloc(&st.d_chan, (size_t)nch * sizeof(sddc::ChDemChannel));
+        for (float2 *&p : st.d_last)
+            if (e == hipSuccess) e = hipMalloc(&p, (size_t)nch * sizeof(float2));
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            st.clear();
+            return fail(SDDC_ERR_NOMEM, "channel demodulator: no device memory for %d channels", nch);
+        }
+        e = hipMemcpy(st.d_chan, chan.data(), (size_t)nch * sizeof(sddc::ChDemChannel), hipMemcpyHostToDevice);
+        // zeroed on the handle's stream and waited for: the first launch may be on any stream
+        if (e == hipSuccess) e = hipMemsetAsync(st.d_last[0], 0, (size_t)nch * sizeof(float2), h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) {
+            st.clear();
+            HIP_TRY(e);
+        }
+    }
+    st.chan = std::move(chan);
+    st.nch = nch;
+    st.out_fmt = out_format;
+    st.pos = 0;
+    return SDDC_OK;
+}
+
+int sddc_ddc_channel_demodulator_reset(sddc_ddc_t *h)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    ChannelDemod &st = h->chdem;
+    if (st.chan.empty()) return fail(SDDC_ERR_STATE, "channel demodulator reset: no demodulator set");
+    if (h->cpu) {
+        std::fill(st.last_h.begin(), st.last_h.end(), 0.f);
+    } else {
+        DeviceGuard g(h->device);
+        HIP_TRY(g.err);
+        HIP_TRY(st.readers.sync());   // earlier launches, on any stream, may still use the last samples
+        HIP_TRY(hipMemsetAsync(st.d_last[st.cur], 0, (size_t)st.nch * sizeof(float2), h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));   // the next launch may be on any stream
+    }
+    st.pos = 0;
+    return SDDC_OK;
+}
+
+// the checks both calls share (under h->mu: the formats and the demodulator are read here)
+static int check_chdem_args(const sddc_ddc_t *h, const void *iq, int nch, size_t nsamp, size_t in_stride,
+                            const void *out, size_t out_stride, const float *power)
+{
+    const ChannelDemod &st = h->chdem;
+    if (st.chan.empty()) return fail(SDDC_ERR_STATE, "channel demodulate: no demodulator set");
+    if (nch != st.nch)
+        return fail(SDDC_ERR_STATE, "channel demodulate: the demodulator is set for %d channels, the call has %d", st.nch,
+                    nch);
+    if (nsamp == 0 || nsamp > ((size_t)1 << 40)) return fail(SDDC_ERR_ARG, "nsamp must be in 1..2^40 (got %zu)", nsamp);
+    if (nch > 1 && (in_stride < 2 * nsamp || (in_stride & 1) != 0))
+        return fail(SDDC_ERR_ARG, "in_stride must be even and >= 2 nsamp (got %zu, nsamp %zu)", in_stride, nsamp);
+    if (nch > 1 && out_stride < nsamp)
+        return fail(SDDC_ERR_ARG, "out_stride must be >= nsamp (got %zu, nsamp %zu)", out_stride, nsamp);
+    if (!iq || !out) return fail(SDDC_ERR_ARG, "null buffer");
+    const uintptr_t sample = h->out_fmt == SDDC_DDC_FMT_CS16 ? 4 : 8;
+    if (((uintptr_t)iq & (sample - 1)) != 0) return fail(SDDC_ERR_ARG, "iq must be %d-byte aligned", (int)sample);
+    const uintptr_t es = st.out_fmt == SDDC_DDC_AUDIO_S16 ? 2 : 4;
+    if (((uintptr_t)out & (es - 1)) != 0) return fail(SDDC_ERR_ARG, "the output must be %d-byte aligned", (int)es);
+    if (((uintptr_t)power & 3) != 0) return fail(SDDC_ERR_ARG, "the power array must be 4-byte aligned");
+    return SDDC_OK;
+}
+
+// One launch on s: it reads the current last samples and writes the other buffer, so it runs after
+// every earlier launch of the handle, whatever its stream; the buffers swap and the position
+// advances once it is enqueued.
+static int chdem_launch(sddc_ddc_t *h, const void *d_iq, int nch, size_t nsamp, size_t in_stride, void *d_out,
+                        size_t out_stride, float *d_power, hipStream_t s)
+{
+    ChannelDemod &st = h->chdem;
+    if (d_power) {
+        const size_t need = (size_t)nch * sddc::channel_demod_tiles(nsamp);
+        if (need > st.partial_cap) {
+            HIP_TRY(st.readers.sync());   // an earlier launch may still add its tile sums
+            if (int rc = grow_device_buffer(&st.d_partial, &st.partial_cap, need, "channel demodulate", "tile sums")) return rc;
+        }
+    }
+    HIP_TRY(st.readers.order_before(s));
+    const hipError_t e = sddc::launch_channel_demod(h->tables, d_iq, h->out_fmt == SDDC_DDC_FMT_CS16, h->cs16_scale, nch,
+                                                    nsamp, in_stride, st.d_chan, st.pos, st.d_last[st.cur],
+                                                    st.d_last[st.cur ^ 1], d_out, st.out_fmt == SDDC_DDC_AUDIO_S16,
+                                                    out_stride, d_power, st.d_partial, st.max_wgs, h->device, s);
+    const hipError_t er = st.readers.record(s);   // whatever was enqueued stays ordered
+    HIP_TRY(e);
+    st.cur ^= 1;
+    st.pos += (uint32_t)nsamp;
+    HIP_TRY(er);
+    return SDDC_OK;
+}
+
+int sddc_ddc_channel_demodulate_device(sddc_ddc_t *h, const void *d_iq, int nch, size_t nsamp, size_t in_stride,
+                                       void *d_out, size_t out_stride, float *d_power, void *hip_stream)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(h->mu);   // the call reads the formats and the demodulator: one consistent set
+    if (h->cpu) return fail(SDDC_ERR_STATE, "channel_demodulate_device: a CPU handle has no device path");
+    if (int rc = check_chdem_args(h, d_iq, nch, nsamp, in_stride, d_out, out_stride, d_power)) return rc;
+    DeviceGuard g(h->device);
+    HIP_TRY(g.err);
+    return chdem_launch(h, d_iq, nch, nsamp, in_stride, d_out, out_stride, d_power, (hipStream_t)hip_stream);
+}
+
+int sddc_ddc_channel_demodulate_host(sddc_ddc_t *h, const void *iq, int nch, size_t nsamp, size_t in_stride, void *out,
+                                     size_t out_stride, float *power)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (int rc = check_chdem_args(h, iq, nch, nsamp, in_stride, out, out_stride, power)) return rc;
+    ChannelDemod &st = h->chdem;
+    const bool cs16 = h->out_fmt == SDDC_DDC_FMT_CS16, s16 = st.out_fmt == SDDC_DDC_AUDIO_S16;
+    if (h->cpu) {
+        sddc::cpu::R2iq::channel_demodulate(iq, cs16, (float)(1.0 / (double)h->cs16_scale), nch, nsamp,
+                                            nch > 1 ? in_stride : 0, st.chan.data(), st.pos, st.last_h.data(), out, s16,
+                                            nch > 1 ? out_stride : 0, power);
+        st.pos += (uint32_t)nsamp;
+        return SDDC_OK;
+    }
+    DeviceGuard g(h->device);
+    HIP_TRY(g.err);
+    // the spans that hold every channel's samples and outputs
+    const size_t es = s16 ? 2 : 4;
+    const size_t in_bytes = ((size_t)(nch - 1) * (nch > 1 ? in_stride : 0) + 2 * nsamp) * (cs16 ? 2 : 4);
+    const size_t out_bytes = ((size_t)(nch - 1) * (nch > 1 ? out_stride : 0) + nsamp) * es;
+    if (int rc = grow_device_buffer(&st.d_in, &st.in_cap, in_bytes, "channel_demodulate_host", "input bytes")) return rc;
+    if (int rc = grow_device_buffer(&st.d_out, &st.out_cap, out_bytes, "channel_demodulate_host", "output bytes")) return rc;
+    if (power)
+        if (int rc = grow_device_buffer(&st.d_pow, &st.pow_cap, (size_t)nch, "channel_demodulate_host", "powers")) return rc;
+    HIP_TRY(hipMemcpyAsync(st.d_in, iq, in_bytes, hipMemcpyHostToDevice, h->stream));
+    const int rc = chdem_launch(h, st.d_in, nch, nsamp, in_stride, st.d_out, out_stride, power ? st.d_pow : nullptr, h->stream);
+    if (rc == SDDC_OK) {   // the streams alone: the caller's memory between them stays as it is
+        if (nch == 1 || out_stride == nsamp)
+            HIP_TRY(hipMemcpyAsync(out, st.d_out, out_bytes, hipMemcpyDeviceToHost, h->stream));
+        else
+            HIP_TRY(hipMemcpy2DAsync(out, out_stride * es, st.d_out, out_stride * es, nsamp * es, (size_t)nch,
+                                     hipMemcpyDeviceToHost, h->stream));
+        if (power) HIP_TRY(hipMemcpyAsync(power, st.d_pow, (size_t)nch * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(h->stream));   // also after a failed launch: the caller's input is free again
     return rc;
 }
 

@@ -64,6 +64,11 @@ extern "C" {
  * loop.  The grid changes no output bit (tests). */
 #define SDDC_DDC_PARAM_CHRES_MAX_WGS 14
 
+/* SDDC_DDC_PARAM_CHDEM_MAX_WGS = n > 0: the channel demodulator kernel's grid is at most n workgroups,
+ * as params 13 and 14 for the decimator and the resampler; 0 (default): one workgroup per item, or
+ * full residency with a loop.  The grid changes no output bit and no power bit (tests). */
+#define SDDC_DDC_PARAM_CHDEM_MAX_WGS 15
+
 int sddc_ddc_internal_set_param(sddc_ddc_t *h, int param, int value);
 /* A given table of n relative shares (n = the d = 0 kernel's full-residency grid, 4 x CUs) used as
  * it is, without clamps or measurements, until n = 0 clears it (tests). */
@@ -85,6 +90,15 @@ int sddc_ddc_internal_chres_layout(int up, int down, int ntaps, int cs16, int *t
 /* Set the resampler's stream position to pos samples consumed (any value: it is kept reduced), the
  * tails left as they are: tests start a stream far out.  SDDC_ERR_STATE: no resampler set. */
 int sddc_ddc_internal_chres_set_position(sddc_ddc_t *h, uint64_t pos);
+/* Set the demodulator's stream position (the index that the BFO phase w * (p + i) counts from), the
+ * last samples left as they are: tests start a stream next to the 2^32 wrap.  SDDC_ERR_STATE: no
+ * demodulator set. */
+int sddc_ddc_internal_chdem_set_position(sddc_ddc_t *h, uint32_t pos);
+/* demod_math.h's two routines as the CPU backend compiles them, on arrays of n values: out[i] =
+ * angle(im[i], re[i]); (c[i], s[i]) = cos and sin of 2 pi words[i] / 2^32 (the accuracy sweeps of
+ * tests/test_channel_demod_cpu.py; no handle, no device). */
+int sddc_ddc_internal_demod_angle(const float *im, const float *re, size_t n, float *out);
+int sddc_ddc_internal_demod_sincos(const uint32_t *words, size_t n, float *c, float *s);
 /* The controller alone (no handle, no device): tests/test_adaptive_split.py. */
 void *sddc_fs_split_create(int G, unsigned slot_weights);
 void sddc_fs_split_destroy(void *c);

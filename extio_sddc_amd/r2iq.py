@@ -131,6 +131,17 @@ def resample_count(up: int, down: int, pos: int, nsamp: int) -> int:
     return int(_lib.load().sddc_ddc_resample_count(int(up), int(down), int(pos) & (2 ** 64 - 1), int(nsamp)))
 
 
+DEMOD_AM, DEMOD_FM, DEMOD_BFO = 0, 1, 2   # SDDC_DDC_DEMOD_*
+AUDIO_F32, AUDIO_S16 = 0, 1               # SDDC_DDC_AUDIO_*
+CHANNEL_DEMOD_TILE = 2048                 # ddc_kernels.h kChDemTile: the demodulator kernel's samples per tile
+
+
+def bfo_word(rel: float) -> int:
+    """The BFO phase increment of a frequency of rel cycles per sample, rel in [-0.5, 0.5):
+    round(rel * 2^32) mod 2^32 (sddc_ddc_bfo_word)."""
+    return int(_lib.load().sddc_ddc_bfo_word(float(rel)))
+
+
 def psd_to_dbfs(psd) -> np.ndarray:
     """R2iq.spectrum's output in dB relative to a full-scale real tone (amplitude 32768 reads
     32768^2 / 4 at its bin centre): 10 log10(4 psd / 32768^2); -inf where psd is 0."""
@@ -159,6 +170,7 @@ class R2iq:
         self._fmt = FMT_CF32
         self._decim = None   # (ntaps, factor, nch) of setChannelDecimator
         self._resamp = None  # (ntaps, up, down, nch) of setChannelResampler
+        self._demod = None   # (nch, out_format) of setChannelDemodulator
 
     # -- lifecycle --------------------------------------------------------
     @property
@@ -542,6 +554,84 @@ class R2iq:
                                                        d_out.data_ptr(), out_stride, ctypes.addressof(got),
                                                        _stream_handle(stream)))
         return int(got.value)
+
+    # -- channel demodulator ------------------------------------------------------
+    def setChannelDemodulator(self, modes, gains=None, bfo_words=None, out_format: int = AUDIO_F32) -> None:
+        """The streaming demodulator of channel_demodulate: per channel a mode (DEMOD_AM: g |x|,
+        DEMOD_FM: g angle(x[i] conj(x[i - 1])), DEMOD_BFO: g Re(x[i] e^{j 2 pi w (p + i) / 2^32})), a
+        finite gain (default 1) and a BFO word (default 0, see bfo_word); out_format AUDIO_F32 or
+        AUDIO_S16 (rounded to nearest even and clamped).  Every call zeroes the kept last samples and
+        the stream position.  modes=None turns the demodulator off."""
+        if modes is None or len(modes) == 0:
+            check(self._L.sddc_ddc_set_channel_demodulator(self._h, None, None, None, 0, 0))
+            self._demod = None
+            return
+        m = np.ascontiguousarray(np.asarray(modes, np.int32).reshape(-1))
+        g = None if gains is None else np.ascontiguousarray(np.asarray(gains, np.float32).reshape(-1))
+        w = None if bfo_words is None else np.ascontiguousarray(
+            (np.asarray(bfo_words, np.int64).reshape(-1) & 0xffffffff).astype(np.uint32))
+        if (g is not None and g.size != m.size) or (w is not None and w.size != m.size):
+            raise DDCError(-1, "gains and bfo_words must have one value per mode")
+        check(self._L.sddc_ddc_set_channel_demodulator(self._h, m.ctypes.data, None if g is None else g.ctypes.data,
+                                                       None if w is None else w.ctypes.data, m.size, int(out_format)))
+        self._demod = (m.size, int(out_format))
+
+    def resetChannelDemodulator(self) -> None:
+        """Zero every channel's last sample and the stream position: the next call starts a new stream."""
+        check(self._L.sddc_ddc_channel_demodulator_reset(self._h))
+
+    def channel_demodulate(self, iq: np.ndarray, power: bool = False):
+        """The demodulator on host arrays: iq is complex64 [nch, nsamp] (CF32) or int16 [nch, nsamp, 2]
+        (CS16), matching the handle's output format, any nsamp >= 1; a single stream may drop the
+        channel axis.  Returns float32 (AUDIO_S16: int16) [nch, nsamp], with power=True also the
+        float32 [nch] mean of |x|^2 over this call, and keeps each channel's last sample and the
+        position for the next call."""
+        if self._demod is None:
+            raise DDCError(-4, "no channel demodulator set")
+        iq, nch, nsamp = self._channel_host_array(iq)
+        if nsamp < 1:
+            raise DDCError(-1, "nsamp must be >= 1")
+        out = np.empty((nch, nsamp), np.int16 if self._demod[1] == AUDIO_S16 else np.float32)
+        pw = np.empty(nch, np.float32) if power else None
+        check(self._L.sddc_ddc_channel_demodulate_host(self._h, iq.ctypes.data, nch, nsamp, 2 * nsamp, out.ctypes.data,
+                                                       nsamp, None if pw is None else pw.ctypes.data))
+        return (out, pw) if power else out
+
+    def channel_demodulate_device(self, d_iq, nch: int, nsamp: int, in_stride: int, d_out, out_stride: int,
+                                  d_power=None, stream=None) -> None:
+        """The demodulator on the buffer process_channels_device, channel_decimate_device or
+        channel_resample_device wrote: d_iq is a float32 (CS16: int16) device tensor, channel c at
+        c * in_stride components, nsamp complex samples each; d_out float32 (AUDIO_S16: int16),
+        channel c's nsamp outputs at c * out_stride samples; d_power None or a float32 device tensor
+        of nch values.  Enqueued on `stream` like process_device; the calls of one handle run in call
+        order."""
+        import torch
+        if self._demod is None:
+            raise DDCError(-4, "no channel demodulator set")
+        if nch < 1 or nsamp < 1:
+            raise DDCError(-1, "nch and nsamp must be >= 1")
+        if not (d_iq.is_cuda and d_out.is_cuda and (d_power is None or d_power.is_cuda)):
+            raise DDCError(-1, "device path needs device tensors")
+        want = torch.int16 if self._fmt == FMT_CS16 else torch.float32
+        want_out = torch.int16 if self._demod[1] == AUDIO_S16 else torch.float32
+        if d_iq.dtype != want or d_out.dtype != want_out:
+            raise DDCError(-1, f"d_iq must be {want} and d_out {want_out}")
+        if not (d_iq.is_contiguous() and d_out.is_contiguous()):
+            raise DDCError(-1, "tensors must be contiguous")
+        need = (nch - 1) * in_stride + 2 * nsamp
+        if d_iq.numel() < need:
+            raise DDCError(-1, f"d_iq has {d_iq.numel()} components, need {need}")
+        need = (nch - 1) * out_stride + nsamp
+        if d_out.numel() < need:
+            raise DDCError(-1, f"d_out has {d_out.numel()} samples, need {need}")
+        if d_power is not None and (d_power.dtype != torch.float32 or not d_power.is_contiguous()
+                                    or d_power.numel() < nch):
+            raise DDCError(-1, f"d_power must be a contiguous float32 tensor of at least {nch} values")
+        check(self._L.sddc_ddc_channel_demodulate_device(self._h, d_iq.data_ptr(), nch, nsamp, in_stride,
+                                                         d_out.data_ptr(), out_stride,
+                                                         None if d_power is None else d_power.data_ptr(),
+                                                         _stream_handle(stream)))
+
 
 
 def _check_device_buffers(d_in, nblk, d_out, out_floats, fmt=0):

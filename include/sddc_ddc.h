@@ -54,7 +54,9 @@ extern "C" {
                                        channel_decimate_host (new symbols only);
                                        still 3: + set_channel_resampler, channel_resampler_reset,
                                        resample_count, channel_resample_samples,
-                                       channel_resample_device, channel_resample_host (new symbols only) */
+                                       channel_resample_device, channel_resample_host (new symbols only);
+                                       still 3: + bfo_word, set_channel_demodulator, channel_demodulator_reset,
+                                       channel_demodulate_device, channel_demodulate_host (new symbols only) */
 
 #define SDDC_DDC_HALF_FFT   4096    /* halfFft               fft_mt_r2iq.h:18 */
 #define SDDC_DDC_FFTN       8192    /* FFTN_R_ADC            config.h:49 */
@@ -409,6 +411,84 @@ int sddc_ddc_channel_resample_device(sddc_ddc_t *h, const void *d_iq, int nch, s
  * definition and bound (another fixed order of the sum, also independent of the cut). */
 int sddc_ddc_channel_resample_host(sddc_ddc_t *h, const void *iq, int nch, size_t nsamp, size_t in_stride,
                                    float *out, size_t out_stride, size_t *nout);
+
+/* ---- channel demodulator: streaming AM / FM / BFO audio from the channel streams -----------
+ * The last link of the chain DDC -> decimator -> resampler: real audio (or a discriminator / product
+ * detector output) from every channel stream, on the device, continuous across calls.  For channel c
+ * with mode m_c, gain g_c (a finite float), 32-bit phase increment w_c, stream index i = 0, 1, ..
+ * since the last set or reset, sample values x_c[i] = (I, Q) read exactly as the decimator reads them
+ * (the handle's CURRENT output format, CS16 as (float)v * (float)(1.0 / (double)cs16_scale)) and
+ * x_c[-1] = 0:
+ *   SDDC_DDC_DEMOD_AM   y = g * sqrtf(fmaf(I, I, Q*Q))
+ *   SDDC_DDC_DEMOD_FM   the quadrature discriminator: with (I', Q') = x_c[i-1],
+ *                       re = fmaf(I, I', Q*Q'),  im = fmaf(Q, I', -(I*Q')),  y = g * angle(im, re);
+ *                       angle(0, 0) = +0.0f, so y_c[0] of a new stream is zero.  A tone e^{j 2 pi f i}
+ *                       reads g * 2 pi f; for NBFM g = fs / (2 pi deviation) gives +-1 at full deviation.
+ *   SDDC_DDC_DEMOD_BFO  the product detector (real part after a rotation):
+ *                       phi_i = 2 pi ((w_c * (p + i)) mod 2^32) / 2^32, p the stream position, in
+ *                       exact 32-bit modular arithmetic;  y = g * fmaf(I, cos phi_i, -(Q * sin phi_i)).
+ *                       w = 0 gives y = g*I exactly, w = 2^30 the sequence g*I, -g*Q, -g*I, g*Q
+ *                       exactly (the sine and cosine are exact at quarter cycles).  With the
+ *                       per-channel fine-tune NCO and the decimator's real low-pass this is the third
+ *                       step of a Weaver SSB / CW demodulator.
+ * angle and the sine / cosine of a phase word are this library's own routines (csrc/demod_math.h):
+ * fixed sequences of correctly rounded float operations (fmaf, +, *, /, sqrtf; no libm), the same
+ * text on the device and in the CPU backend.  angle is within 4 ulp of the true angle (<= 8 u |theta|,
+ * u = 2^-24), the sine and cosine within 4 u absolute, the rounding of the phase included.  So a GPU
+ * handle and a CPU handle produce BIT-IDENTICAL demodulated samples in all three modes and both
+ * output formats, for inputs whose components are 0 or of magnitude in [2^-40, 2^40] (no subnormal
+ * intermediate).  Against the float64 value y64 of the same float32 sample values:
+ *   AM   |y - y64| <= 4 u |y64|
+ *   FM   |y - g theta64| <= |g| (4 u + 8 u |theta64|)      where |x[i]| |x[i-1]| > 0
+ *   BFO  |y - y64| <= |g| (|I| + |Q|) 6 u
+ * Output: SDDC_DDC_AUDIO_F32 writes y; SDDC_DDC_AUDIO_S16 writes y rounded to nearest even and
+ * clamped to [-32768, 32767], NaN as 0.  Channel c's nsamp outputs start c*out_stride output samples
+ * into the output (for nch > 1 out_stride >= nsamp, any parity), which is aligned to one output sample
+ * (4 or 2 bytes).  Nothing is written between the streams or outside them; an S16 stream with an odd
+ * start or length is finished with 2-byte stores.  Input: layout, strides and alignment exactly as
+ * for the channel decimator; nsamp is any value >= 1 (at most 2^40).
+ * Channel power (squelch, scanner): power may be NULL, else nch floats that receive
+ *   P_c = (sum_i fmaf(I, I, Q*Q)) * (float)(1.0 / (double)nsamp)
+ * over THIS call's samples, summed in an order that depends on nsamp only (fixed tile sums added in
+ * a fixed order, no float atomics): bit-identical from run to run, for any grid and for a channel
+ * alone or among others; a per-call figure, so not cut-invariant.  |P - P64| <= gamma_n P64 with
+ * n = nsamp + 3, gamma_n = n u / (1 - n u); a GPU and a CPU handle agree within twice that.
+ * State per handle, independent of the decimator's and the resampler's: each channel's last sample
+ * value as float32 (I, Q) (on the device for a GPU handle), and one stream position shared by all
+ * channels, kept on the host modulo 2^32, so a stream of any length overflows nothing.  A demodulated
+ * sample depends only on its own sample value, the one before it and its stream index: it is
+ * bit-identical from run to run, on any stream, for any grid, for a channel alone or among others, and
+ * for any cut of the same samples into calls. */
+#define SDDC_DDC_DEMOD_AM  0
+#define SDDC_DDC_DEMOD_FM  1
+#define SDDC_DDC_DEMOD_BFO 2
+#define SDDC_DDC_AUDIO_F32 0
+#define SDDC_DDC_AUDIO_S16 1
+/* round(relative_freq * 2^32) mod 2^32: the BFO word of a frequency in cycles per sample,
+ * relative_freq in [-0.5, 0.5) (other values are taken modulo 1; not finite: 0).  Stateless. */
+uint32_t sddc_ddc_bfo_word(double relative_freq);
+/* modes: host array of nch values SDDC_DDC_DEMOD_*; gains: nch finite floats (NULL: all 1);
+ * bfo_words: nch phase increments (NULL: all 0; read in BFO mode only); 1 <= nch <=
+ * SDDC_DDC_MAX_CHANNELS; out_format SDDC_DDC_AUDIO_*; a violation returns SDDC_ERR_ARG.  modes NULL
+ * or nch == 0 turns the demodulator off and frees its state.  Every set call zeroes the last samples
+ * and the position.  A change waits for the handle's demodulator launches in flight. */
+int sddc_ddc_set_channel_demodulator(sddc_ddc_t *h, const int *modes, const float *gains, const uint32_t *bfo_words,
+                                     int nch, int out_format);
+/* zero every channel's last sample and the position: the next call starts a new stream
+ * (SDDC_ERR_STATE: no demodulator set) */
+int sddc_ddc_channel_demodulator_reset(sddc_ddc_t *h);
+/* GPU handles; enqueued on hip_stream, returns after launch.  d_power: NULL or nch device floats.
+ * SDDC_ERR_STATE: no demodulator set, another nch than the set one, a CPU handle.  SDDC_ERR_ARG:
+ * nsamp == 0 or above 2^40, a bad stride or alignment, a null buffer.  A failed call changes no state.
+ * The calls of one handle share the last samples and the position: they run one after the other in
+ * call order, whatever their streams. */
+int sddc_ddc_channel_demodulate_device(sddc_ddc_t *h, const void *d_iq, int nch, size_t nsamp, size_t in_stride,
+                                       void *d_out, size_t out_stride, float *d_power, void *hip_stream);
+/* Host buffers, the same layouts.  GPU handle: copy in, kernel, copy back, synchronous; it advances
+ * the same device state as the device call.  CPU handle: the same definition through the same
+ * arithmetic header, sample by sample; its power is summed in sample order. */
+int sddc_ddc_channel_demodulate_host(sddc_ddc_t *h, const void *iq, int nch, size_t nsamp, size_t in_stride,
+                                     void *out, size_t out_stride, float *power);
 
 /* ---- ingest ---------------------------------------
  * Pin a caller-owned host region (hipHostRegister) so the host path DMAs blocks
