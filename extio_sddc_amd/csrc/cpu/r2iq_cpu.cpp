@@ -482,5 +482,51 @@ void R2iq::demod_sincos_n(const uint32_t *words, size_t n, float *c, float *s)
     for (size_t i = 0; i < n; i++) demod::demod_sincos_word(words[i], c + i, s + i);
 }
 
+// The channel audio filter: audio_iir_math.h's stream, sample by sample.
+template <int S>
+static void channel_audio_filter_s(const void *in, bool in16, int nch, size_t nsamp, size_t in_stride, const float *coef,
+                                   const float *mat, unsigned block_pos, float *state, void *out, bool out16,
+                                   size_t out_stride)
+{
+    constexpr int N = 2 * S;
+    for (int c = 0; c < nch; c++) {
+        const float *xf = static_cast<const float *>(in) + (size_t)c * in_stride;
+        const int16_t *xs = static_cast<const int16_t *>(in) + (size_t)c * in_stride;
+        float *yf = static_cast<float *>(out) + (size_t)c * out_stride;
+        int16_t *ys = static_cast<int16_t *>(out) + (size_t)c * out_stride;
+        const float *cf = coef + (size_t)c * 5 * S, *M = mat + (size_t)c * N * N;
+        float *E = state + (size_t)c * 3 * N, *R = E + N, *Zr = R + N;
+        unsigned n = block_pos;
+        for (size_t i = 0; i < nsamp; i++) {
+            const float x = in16 ? (float)xs[i] : xf[i];
+            const float y = audio::audio_step<S>(cf, R, x);
+            (void)audio::audio_step<S>(cf, Zr, x);
+            if (out16) ys[i] = demod::demod_s16(y);
+            else yf[i] = y;
+            if (++n == (unsigned)audio::kAudioBlock) {
+                float nE[N];
+                audio::audio_adv<S>(M, E, Zr, nE);
+                for (int q = 0; q < N; q++) {
+                    E[q] = R[q] = nE[q];
+                    Zr[q] = 0.f;
+                }
+                n = 0;
+            }
+        }
+    }
+}
+
+void R2iq::channel_audio_filter(const void *in, bool in16, int nch, int nsec, size_t nsamp, size_t in_stride,
+                                const float *coef, const float *mat, unsigned block_pos, float *state, void *out,
+                                bool out16, size_t out_stride)
+{
+    switch (nsec) {
+    case 1: return channel_audio_filter_s<1>(in, in16, nch, nsamp, in_stride, coef, mat, block_pos, state, out, out16, out_stride);
+    case 2: return channel_audio_filter_s<2>(in, in16, nch, nsamp, in_stride, coef, mat, block_pos, state, out, out16, out_stride);
+    case 3: return channel_audio_filter_s<3>(in, in16, nch, nsamp, in_stride, coef, mat, block_pos, state, out, out16, out_stride);
+    default: return channel_audio_filter_s<4>(in, in16, nch, nsamp, in_stride, coef, mat, block_pos, state, out, out16, out_stride);
+    }
+}
+
 }  // namespace cpu
 }  // namespace sddc

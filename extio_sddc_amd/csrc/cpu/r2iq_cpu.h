@@ -23,6 +23,7 @@
 #include <memory>
 #include <vector>
 
+#include "../audio_iir_math.h"
 #include "../demod_math.h"
 #include "fft_avx2.hpp"
 
@@ -92,6 +93,14 @@ public:
     static void channel_demodulate(const void *iq, bool cs16, float inv_s, int nch, size_t nsamp, size_t in_stride,
                                    const ChDemChannel *chan, uint32_t pos, float *last, void *out, bool s16,
                                    size_t out_stride, float *power);
+    // The channel audio filter (sddc_ddc.h, sddc_ddc_channel_audio_filter_host; audio_iir_math.h): channel
+    // c's nsamp samples (float, or int16 when in16, at in + c * in_stride samples) through its nsec
+    // sections coef [nch][nsec][5] with the block matrices mat [nch][2 nsec][2 nsec]; the call's first
+    // sample is block_pos samples into a block.  state: [nch][3][2 nsec] floats (E, R, Zr) before the
+    // call, replaced by the ones after it.  Outputs float, or int16 when out16, at out + c * out_stride.
+    static void channel_audio_filter(const void *in, bool in16, int nch, int nsec, size_t nsamp, size_t in_stride,
+                                     const float *coef, const float *mat, unsigned block_pos, float *state, void *out,
+                                     bool out16, size_t out_stride);
     // demod_math.h's routines on arrays (the accuracy sweeps of tests/test_channel_demod_cpu.py)
     static void demod_angle_n(const float *im, const float *re, size_t n, float *out);
     static void demod_sincos_n(const uint32_t *words, size_t n, float *c, float *s);

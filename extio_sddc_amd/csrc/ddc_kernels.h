@@ -266,6 +266,25 @@ hipError_t launch_channel_demod(const KernelTables &t, const void *d_iq, int cs1
                                 const float2 *d_last_in, float2 *d_last_out, void *d_out, int s16, size_t out_stride,
                                 float *d_power, float *d_partial, int max_wgs, int device, hipStream_t s);
 
+// Channel audio filter (ddc_channel_audio.hip, sddc_ddc_channel_audio_filter_device): one run of the
+// block-form biquad cascade (audio_iir_math.h) over nch real streams of nsamp >= 1 samples, float
+// (in_s16 = 0) or int16 read as (float)v, channel c at c * in_stride samples, aligned to one sample;
+// outputs float or int16 (demod_s16) at c * out_stride samples.  block_pos: the stream position of
+// the run's first sample mod kAudioBlock.  d_coef: [nch][nsec][5]; d_mat: [nch][2 nsec][2 nsec];
+// d_state_in / d_state_out: [nch][3][2 nsec] floats (E, R, Zr) before / after the run (two buffers);
+// d_scratch: 2 nsec floats per (channel, full block of the run), may be null when the run holds no
+// full block (channel_audio_blocks).  Three launches on s; max_wgs > 0 caps their grids (tests).  The
+// caller has checked the strides.
+inline size_t channel_audio_blocks(unsigned block_pos, size_t nsamp)
+{
+    const size_t to_edge = (256u - block_pos) % 256u;
+    return nsamp > to_edge ? (nsamp - to_edge) / 256u : 0;
+}
+hipError_t launch_channel_audio(const KernelTables &t, const void *d_in, int in_s16, int nch, int nsec, size_t nsamp,
+                                size_t in_stride, unsigned block_pos, const float *d_coef, const float *d_mat,
+                                const float *d_state_in, float *d_state_out, float *d_scratch, void *d_out, int out_s16,
+                                size_t out_stride, int max_wgs, int device, hipStream_t s);
+
 // batched FFTs (fft_batch.hip, include/sddc_fft.h); fft_prepare fills the device's twiddle
 // table once (synchronises s the first time)
 hipError_t fft_prepare(hipStream_t s);

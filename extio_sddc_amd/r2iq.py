@@ -142,6 +142,21 @@ def bfo_word(rel: float) -> int:
     return int(_lib.load().sddc_ddc_bfo_word(float(rel)))
 
 
+AUDIO_BLOCK = 256                         # SDDC_DDC_AUDIO_BLOCK: the audio filter's block length B
+AUDIO_MAX_SECTIONS = 4                    # SDDC_DDC_AUDIO_MAX_SECTIONS
+(BIQUAD_IDENTITY, BIQUAD_DC_BLOCK, BIQUAD_ONE_POLE_LP, BIQUAD_LOWPASS, BIQUAD_HIGHPASS,
+ BIQUAD_NOTCH) = range(6)                 # SDDC_DDC_BIQUAD_*
+
+
+def biquad(kind: int, f: float = 0.25, q: float = 0.7071067811865476) -> np.ndarray:
+    """One section (b0, b1, b2, a1, a2) as float32 (sddc_ddc_biquad): kind BIQUAD_*, f in cycles per
+    sample in (0, 0.5), q read by LOWPASS, HIGHPASS and NOTCH.  DC_BLOCK: the corner; ONE_POLE_LP: a
+    de-emphasis of time constant tau at sample rate fs is f = 1 / (2 pi tau fs)."""
+    c = np.zeros(5, np.float32)
+    check(_lib.load().sddc_ddc_biquad(int(kind), float(f), float(q), c.ctypes.data))
+    return c
+
+
 def psd_to_dbfs(psd) -> np.ndarray:
     """R2iq.spectrum's output in dB relative to a full-scale real tone (amplitude 32768 reads
     32768^2 / 4 at its bin centre): 10 log10(4 psd / 32768^2); -inf where psd is 0."""
@@ -171,6 +186,7 @@ class R2iq:
         self._decim = None   # (ntaps, factor, nch) of setChannelDecimator
         self._resamp = None  # (ntaps, up, down, nch) of setChannelResampler
         self._demod = None   # (nch, out_format) of setChannelDemodulator
+        self._audio = None   # (nch, in_format, out_format) of setChannelAudioFilter
 
     # -- lifecycle --------------------------------------------------------
     @property
@@ -632,6 +648,74 @@ class R2iq:
                                                          None if d_power is None else d_power.data_ptr(),
                                                          _stream_handle(stream)))
 
+
+    # -- channel audio filter -------------------------------------------------------
+    def setChannelAudioFilter(self, coeffs, in_format: int = AUDIO_F32, out_format: int = AUDIO_F32) -> None:
+        """The streaming biquad cascade of channel_audio_filter: coeffs is float32 [nch, nsec, 5], per
+        section (b0, b1, b2, a1, a2) as biquad() returns them, 1 <= nsec <= AUDIO_MAX_SECTIONS (pad a
+        shorter channel with biquad(BIQUAD_IDENTITY)); every section must be stable.  in_format /
+        out_format AUDIO_F32 or AUDIO_S16.  Every call zeroes the state and the stream position.
+        coeffs=None turns the stage off."""
+        if coeffs is None or np.size(coeffs) == 0:
+            check(self._L.sddc_ddc_set_channel_audio_filter(self._h, None, 0, 0, 0, 0))
+            self._audio = None
+            return
+        c = np.ascontiguousarray(np.asarray(coeffs, np.float32))
+        if c.ndim != 3 or c.shape[2] != 5:
+            raise DDCError(-1, "coeffs must be [nch, nsec, 5]")
+        check(self._L.sddc_ddc_set_channel_audio_filter(self._h, c.ctypes.data, c.shape[1], c.shape[0], int(in_format),
+                                                        int(out_format)))
+        self._audio = (c.shape[0], int(in_format), int(out_format))
+
+    def resetChannelAudioFilter(self) -> None:
+        """Zero every channel's filter state and the stream position: the next call starts a new stream."""
+        check(self._L.sddc_ddc_channel_audio_filter_reset(self._h))
+
+    def channel_audio_filter(self, x: np.ndarray) -> np.ndarray:
+        """The audio filter on a host array: x is float32 (AUDIO_S16 in: int16) [nch, nsamp], any nsamp
+        >= 1; a single stream may drop the channel axis.  Returns float32 (AUDIO_S16 out: int16)
+        [nch, nsamp] and keeps every channel's state for the next call."""
+        if self._audio is None:
+            raise DDCError(-4, "no channel audio filter set")
+        nch, fin, fout = self._audio
+        x = np.asarray(x, np.int16 if fin == AUDIO_S16 else np.float32)
+        if x.ndim == 1:
+            x = x[None, :]
+        x = np.ascontiguousarray(x)
+        if x.ndim != 2 or x.shape[1] < 1:
+            raise DDCError(-1, "x must be [nch, nsamp] with nsamp >= 1")
+        nsamp = x.shape[1]
+        out = np.empty((x.shape[0], nsamp), np.int16 if fout == AUDIO_S16 else np.float32)
+        check(self._L.sddc_ddc_channel_audio_filter_host(self._h, x.ctypes.data, x.shape[0], nsamp, nsamp,
+                                                         out.ctypes.data, nsamp))
+        return out
+
+    def channel_audio_filter_device(self, d_in, nch: int, nsamp: int, in_stride: int, d_out, out_stride: int,
+                                    stream=None) -> None:
+        """The audio filter on the buffer channel_demodulate_device wrote (the same buffer, stride and
+        format): d_in is a float32 (AUDIO_S16 in: int16) device tensor, channel c's nsamp samples at
+        c * in_stride; d_out float32 (AUDIO_S16 out: int16), channel c's outputs at c * out_stride;
+        the two must not overlap.  Enqueued on `stream` like process_device; the calls of one handle
+        run in call order."""
+        import torch
+        if self._audio is None:
+            raise DDCError(-4, "no channel audio filter set")
+        if nch < 1 or nsamp < 1:
+            raise DDCError(-1, "nch and nsamp must be >= 1")
+        if not (d_in.is_cuda and d_out.is_cuda):
+            raise DDCError(-1, "device path needs device tensors")
+        want = torch.int16 if self._audio[1] == AUDIO_S16 else torch.float32
+        want_out = torch.int16 if self._audio[2] == AUDIO_S16 else torch.float32
+        if d_in.dtype != want or d_out.dtype != want_out:
+            raise DDCError(-1, f"d_in must be {want} and d_out {want_out}")
+        if not (d_in.is_contiguous() and d_out.is_contiguous()):
+            raise DDCError(-1, "tensors must be contiguous")
+        for name, t, stride in (("d_in", d_in, in_stride), ("d_out", d_out, out_stride)):
+            need = (nch - 1) * stride + nsamp
+            if t.numel() < need:
+                raise DDCError(-1, f"{name} has {t.numel()} samples, need {need}")
+        check(self._L.sddc_ddc_channel_audio_filter_device(self._h, d_in.data_ptr(), nch, nsamp, in_stride,
+                                                           d_out.data_ptr(), out_stride, _stream_handle(stream)))
 
 
 def _check_device_buffers(d_in, nblk, d_out, out_floats, fmt=0):

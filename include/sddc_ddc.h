@@ -56,7 +56,9 @@ extern "C" {
                                        resample_count, channel_resample_samples,
                                        channel_resample_device, channel_resample_host (new symbols only);
                                        still 3: + bfo_word, set_channel_demodulator, channel_demodulator_reset,
-                                       channel_demodulate_device, channel_demodulate_host (new symbols only) */
+                                       channel_demodulate_device, channel_demodulate_host (new symbols only);
+                                       still 3: + biquad, set_channel_audio_filter, channel_audio_filter_reset,
+                                       channel_audio_filter_device, channel_audio_filter_host (new symbols only) */
 
 #define SDDC_DDC_HALF_FFT   4096    /* halfFft               fft_mt_r2iq.h:18 */
 #define SDDC_DDC_FFTN       8192    /* FFTN_R_ADC            config.h:49 */
@@ -489,6 +491,102 @@ int sddc_ddc_channel_demodulate_device(sddc_ddc_t *h, const void *d_iq, int nch,
  * arithmetic header, sample by sample; its power is summed in sample order. */
 int sddc_ddc_channel_demodulate_host(sddc_ddc_t *h, const void *iq, int nch, size_t nsamp, size_t in_stride,
                                      void *out, size_t out_stride, float *power);
+
+/* ---- channel audio filter: a streaming biquad cascade per channel on the device -----------
+ * What stands between the demodulator and playable audio: DC blocking, de-emphasis, the 300 Hz
+ * high-pass of a voice channel, a notch.  Each of nch real audio streams runs through its own cascade
+ * of S = nsec (1..4, the same count for every channel) biquad sections; a section is five floats
+ * (b0, b1, b2, a1, a2) with a0 = 1, in transposed direct form II; a channel that wants fewer sections
+ * pads with (1, 0, 0, 0, 0), which passes finite values through exactly.  AGC is not here: it is
+ * nonlinear, and the block form below is a property of linear recurrences.
+ * Input: SDDC_DDC_AUDIO_F32, or SDDC_DDC_AUDIO_S16 read as (float)v; output F32, or S16 rounded as
+ * the demodulator rounds it.  The demodulator's output feeds this stage directly: the same buffer,
+ * stride and format.
+ * The definition, which both backends compute bit for bit (csrc/audio_iir_math.h; fmaf and * are the
+ * correctly rounded float operations, nothing is contracted).  One step of the cascade on a state
+ * s[2S] with input x, for k = 0 .. S-1:
+ *     y = fmaf(b0, x, s1);  s1 = fmaf(-a1, y, fmaf(b1, x, s2));  s2 = fmaf(-a2, y, b2 * x);  x = y
+ * and the last y is the output.  With B = SDDC_DDC_AUDIO_BLOCK, A_c the 2S x 2S matrix of one
+ * zero-input step of channel c in exact arithmetic on the float coefficients and M_c = float(A_c^B)
+ * (computed at set time: B zero-input steps in double on each unit vector, every fmaf(a, b, c) as
+ * a * b + c with plain, uncontracted * and +), adv(E, Z)_i is acc = Z_i; for j = 0 .. 2S-1:
+ * acc = fmaf(M_ij, E_j, acc).  Each channel has three state vectors E (the entry state of the
+ * current block), R (the running state) and Zr (the running zero-state state) and one position n, the
+ * samples since the last set or reset, all zero then.  Per sample:
+ *     y[n] = step(x, R);  step(x, Zr) with its output dropped;  n++;
+ *     if n is a multiple of B:  E = adv(E, Zr),  R = E,  Zr = 0.
+ * In exact arithmetic this is the plain recurrence.  In float it differs from it by roundings only,
+ * and a block's outputs depend on the earlier stream through E alone, so the device runs the blocks
+ * of a call in parallel.  The definition never mentions calls, grids or streams: an output sample is
+ * BIT-IDENTICAL for any cut of the same samples into calls, for any grid and run length, on any
+ * stream, for a channel alone or among others, and between a GPU handle and a CPU handle (the CPU
+ * backend sets no FTZ / DAZ and gfx950 code keeps float subnormals, so this includes a decaying
+ * filter's subnormal states).
+ * Accuracy against the float64 plain recurrence y64 on the same float32 coefficients (u = 2^-24), to
+ * first order in u.  A rounding of magnitude at most u |v| is made at each of these values v of a
+ * step of section k: y_k (it enters section k's states through -a1, -a2 and the next sections as
+ * their input), the new s1_k and the inner fmaf(b1, x, s2) (both enter s1_k), the new s2_k and b2 x
+ * (both enter s2_k): 5 roundings per section and sample.  Each adv rounds 2S times per row and uses
+ * M's rounded entries: at most (2S + 1) u (|Z_i| + sum_j |M_ij| |E_j|) enters E_i.  With g_q[m] the
+ * response of the last section's output, m samples later, to a unit error at source q (g = c A^m v_q:
+ * the ABSOLUTE VALUE OF THE POWERS' response, not powers of |A|),
+ *     |y[n] - y64[n]| <= bound[n] = 1.01 * ( sum over sources q and samples t <= n of
+ *                                             u |v_q[t]| |g_q[n - t]|
+ *                                    + sum over boundaries b B <= n and rows i of
+ *                                             (2S + 1) u (|Z_i| + sum_j |M_ij| |E_j|) |g_i[n - b B]| )
+ * where v_q[t] is the running recurrence's value for t in n's own block and the zero-state
+ * recurrence's for t in an earlier block (R restarts from E at every boundary, so only Zr's roundings
+ * of earlier blocks survive).  tools/channel_audio_model.py evaluates it; the 1.01 covers the second
+ * order.  It assumes no subnormal intermediate.  S16 output adds 1/2 and the clamp.
+ * Validity, checked at set time: every coefficient finite, every section strictly inside the
+ * stability triangle |a2| < 1 and |a1| < 1 + a2; anything else returns SDDC_ERR_ARG. */
+#define SDDC_DDC_AUDIO_BLOCK 256
+#define SDDC_DDC_AUDIO_MAX_SECTIONS 4
+#define SDDC_DDC_BIQUAD_IDENTITY    0
+#define SDDC_DDC_BIQUAD_DC_BLOCK    1
+#define SDDC_DDC_BIQUAD_ONE_POLE_LP 2
+#define SDDC_DDC_BIQUAD_LOWPASS     3
+#define SDDC_DDC_BIQUAD_HIGHPASS    4
+#define SDDC_DDC_BIQUAD_NOTCH       5
+/* Stateless section designers, computed in double and rounded to float; f in cycles per sample,
+ * 0 < f < 0.5; q > 0 is read by LOWPASS, HIGHPASS and NOTCH only.  coeffs receives (b0, b1, b2, a1, a2).
+ *   IDENTITY     (1, 0, 0, 0, 0); f and q are not read
+ *   DC_BLOCK     r = exp(-2 pi f): b = ((1+r)/2, -(1+r)/2, 0), a = (-r, 0); b1 = -b0 exactly
+ *   ONE_POLE_LP  alpha = exp(-2 pi f): b0 = 1 - alpha, a1 = -alpha; a de-emphasis of time constant
+ *                tau at sample rate fs is f = 1 / (2 pi tau fs)
+ *   LOWPASS, HIGHPASS, NOTCH  the RBJ cookbook forms with Q = q: w = 2 pi f, alpha = sin w / (2 q),
+ *                a0 = 1 + alpha, a1 = -2 cos w / a0, a2 = (1 - alpha) / a0; LOWPASS b0 = b2 =
+ *                (1 - cos w) / (2 a0), b1 = 2 b0; HIGHPASS b0 = b2 = (1 + cos w) / (2 a0), b1 = -2 b0
+ *                exactly; NOTCH b0 = b2 = 1 / a0, b1 = a1.  |H| = q at f for LOWPASS and HIGHPASS.
+ * DC_BLOCK and HIGHPASS thus reject DC exactly in exact arithmetic.  A bad kind, f or q (NOT finite
+ * included) or a null coeffs returns SDDC_ERR_ARG. */
+int sddc_ddc_biquad(int kind, double f, double q, float coeffs[5]);
+/* coeffs: host array [nch][nsec][5]; 1 <= nsec <= 4; 1 <= nch <= SDDC_DDC_MAX_CHANNELS; in_format and
+ * out_format SDDC_DDC_AUDIO_*; a violation, a coefficient that is not finite or an unstable section
+ * returns SDDC_ERR_ARG and sets nothing.  coeffs NULL or nch == 0 turns the stage off and frees its
+ * state.  Every set call zeroes the state and the position, and waits for the stage's launches in
+ * flight. */
+int sddc_ddc_set_channel_audio_filter(sddc_ddc_t *h, const float *coeffs, int nsec, int nch, int in_format,
+                                      int out_format);
+/* zero every channel's state and the position: the next call starts a new stream (SDDC_ERR_STATE: no
+ * filter set) */
+int sddc_ddc_channel_audio_filter_reset(sddc_ddc_t *h);
+/* GPU handles; enqueued on hip_stream, returns after launch.  Channel c's nsamp samples start
+ * c*in_stride input samples into d_in and its outputs c*out_stride output samples into d_out (for
+ * nch > 1 both strides >= nsamp); the buffers are aligned to one sample of their format and must not
+ * overlap; 1 <= nsamp <= 2^40.  Nothing is written between the streams or outside them.
+ * SDDC_ERR_STATE: no filter set, another nch than the set one, a CPU handle.  SDDC_ERR_ARG: nsamp == 0
+ * or above 2^40, a bad stride or alignment, a null buffer.  A failed call changes no state.  The calls
+ * of one handle share the state and the position: they run one after the other in call order, whatever
+ * their streams.  A long call is processed in runs of a bounded number of blocks (the scratch of a run
+ * is 2 nsec floats per channel and block), which changes no output bit. */
+int sddc_ddc_channel_audio_filter_device(sddc_ddc_t *h, const void *d_in, int nch, size_t nsamp, size_t in_stride,
+                                         void *d_out, size_t out_stride, void *hip_stream);
+/* Host buffers, the same layouts.  GPU handle: copy in, kernels, copy back, synchronous; it advances
+ * the same device state as the device call.  CPU handle: the definition's loop through the same
+ * arithmetic header. */
+int sddc_ddc_channel_audio_filter_host(sddc_ddc_t *h, const void *in, int nch, size_t nsamp, size_t in_stride,
+                                       void *out, size_t out_stride);
 
 /* ---- ingest ---------------------------------------
  * Pin a caller-owned host region (hipHostRegister) so the host path DMAs blocks
