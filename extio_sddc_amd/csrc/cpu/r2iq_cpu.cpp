@@ -528,5 +528,41 @@ void R2iq::channel_audio_filter(const void *in, bool in16, int nch, int nsec, si
     }
 }
 
+// The channel AGC: agc_math.h's stream, sample by sample.
+void R2iq::channel_agc(const void *in, bool in16, int nch, size_t nsamp, size_t in_stride, const float *par,
+                       unsigned block_pos, float *state, void *out, bool out16, size_t out_stride, float *env)
+{
+    for (int c = 0; c < nch; c++) {
+        const float *xf = static_cast<const float *>(in) + (size_t)c * in_stride;
+        const int16_t *xs = static_cast<const int16_t *>(in) + (size_t)c * in_stride;
+        float *yf = static_cast<float *>(out) + (size_t)c * out_stride;
+        int16_t *ys = static_cast<int16_t *>(out) + (size_t)c * out_stride;
+        const float *p = par + (size_t)c * agc::kAgcParams;
+        const float T = p[0], d = p[1], F = p[2], dB = p[3];
+        float *st = state + (size_t)c * 3;
+        float E = st[0], R = st[1], Zr = st[2];
+        unsigned n = block_pos;
+        for (size_t i = 0; i < nsamp; i++) {
+            const float x = in16 ? (float)xs[i] : xf[i];
+            const float a = agc::agc_abs(x);
+            R = agc::agc_env(a, d, R);
+            Zr = agc::agc_env(a, d, Zr);
+            const float y = agc::agc_out(T, F, R, x);
+            if (out16) ys[i] = demod::demod_s16(y);
+            else yf[i] = y;
+            if (++n == (unsigned)agc::kAgcBlock) {
+                E = agc::agc_boundary(dB, E, Zr);
+                R = E;
+                Zr = 0.f;
+                n = 0;
+            }
+        }
+        st[0] = E;
+        st[1] = R;
+        st[2] = Zr;
+        if (env) env[c] = R;
+    }
+}
+
 }  // namespace cpu
 }  // namespace sddc

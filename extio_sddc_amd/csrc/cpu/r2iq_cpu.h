@@ -23,6 +23,7 @@
 #include <memory>
 #include <vector>
 
+#include "../agc_math.h"
 #include "../audio_iir_math.h"
 #include "../demod_math.h"
 #include "fft_avx2.hpp"
@@ -101,6 +102,13 @@ public:
     static void channel_audio_filter(const void *in, bool in16, int nch, int nsec, size_t nsamp, size_t in_stride,
                                      const float *coef, const float *mat, unsigned block_pos, float *state, void *out,
                                      bool out16, size_t out_stride);
+    // The channel AGC (sddc_ddc.h, sddc_ddc_channel_agc_host; agc_math.h): channel c's nsamp samples,
+    // laid out and formatted as for channel_audio_filter, through the peak AGC of par [nch][4] = (T, d,
+    // F, dB); the call's first sample is block_pos samples into a block.  state: [nch][3] floats (E, R,
+    // Zr) before the call, replaced by the ones after it.  env: null, or [nch] floats that receive R
+    // after the call's last sample.
+    static void channel_agc(const void *in, bool in16, int nch, size_t nsamp, size_t in_stride, const float *par,
+                            unsigned block_pos, float *state, void *out, bool out16, size_t out_stride, float *env);
     // demod_math.h's routines on arrays (the accuracy sweeps of tests/test_channel_demod_cpu.py)
     static void demod_angle_n(const float *im, const float *re, size_t n, float *out);
     static void demod_sincos_n(const uint32_t *words, size_t n, float *c, float *s);

@@ -285,6 +285,19 @@ hipError_t launch_channel_audio(const KernelTables &t, const void *d_in, int in_
                                 const float *d_state_in, float *d_state_out, float *d_scratch, void *d_out, int out_s16,
                                 size_t out_stride, int max_wgs, int device, hipStream_t s);
 
+// Channel AGC (ddc_channel_agc.hip, sddc_ddc_channel_agc_device): one run of the max-plus block-form
+// peak AGC (agc_math.h) over nch real streams, laid out and formatted as for the audio filter.
+// block_pos: the stream position of the run's first sample mod kAgcBlock.  d_par: [nch][4] floats
+// (T, d, F, dB), 16-byte aligned; d_state_in / d_state_out: [nch][3] floats (E, R, Zr) before / after
+// the run (two buffers); d_scratch: one float per (channel, full block of the run), may be null when
+// the run holds no full block (channel_audio_blocks counts them: the block lengths are equal); d_env:
+// null, or [nch] floats that receive R after the run's last sample.  Three launches on s; max_wgs > 0
+// caps their grids (tests).  The caller has checked the strides.
+hipError_t launch_channel_agc(const KernelTables &t, const void *d_in, int in_s16, int nch, size_t nsamp, size_t in_stride,
+                              unsigned block_pos, const float *d_par, const float *d_state_in, float *d_state_out,
+                              float *d_scratch, void *d_out, int out_s16, size_t out_stride, float *d_env, int max_wgs,
+                              int device, hipStream_t s);
+
 // batched FFTs (fft_batch.hip, include/sddc_fft.h); fft_prepare fills the device's twiddle
 // table once (synchronises s the first time)
 hipError_t fft_prepare(hipStream_t s);

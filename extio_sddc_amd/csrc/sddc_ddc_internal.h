@@ -79,6 +79,16 @@ extern "C" {
  * param 9 bounds the NCO table; 0: the default (512).  The run length changes no output bit (tests). */
 #define SDDC_DDC_PARAM_CHAUD_RUN_BLOCKS 17
 
+/* SDDC_DDC_PARAM_CHAGC_MAX_WGS = n > 0: each of the channel AGC's three grids is at most n workgroups,
+ * as param 16 for the audio filter; 0 (default): one workgroup per wave of items, or full residency
+ * with a loop.  The grid changes no output bit, no envelope bit and no state bit (tests). */
+#define SDDC_DDC_PARAM_CHAGC_MAX_WGS 18
+
+/* SDDC_DDC_PARAM_CHAGC_RUN_BLOCKS = n in 1..2^20: a channel AGC call is processed in runs of at most
+ * n full blocks per channel (plus a head and a tail), which bounds the scratch of a run, as param 17
+ * for the audio filter; 0: the default (2048).  The run length changes no output bit (tests). */
+#define SDDC_DDC_PARAM_CHAGC_RUN_BLOCKS 19
+
 int sddc_ddc_internal_set_param(sddc_ddc_t *h, int param, int value);
 /* A given table of n relative shares (n = the d = 0 kernel's full-residency grid, 4 x CUs) used as
  * it is, without clamps or measurements, until n = 0 clears it (tests). */
@@ -108,6 +118,10 @@ int sddc_ddc_internal_chdem_set_position(sddc_ddc_t *h, uint32_t pos);
  * SDDC_DDC_AUDIO_BLOCK decides where the blocks end), the states left as they are: tests start a
  * stream inside a block.  SDDC_ERR_STATE: no filter set. */
 int sddc_ddc_internal_chaud_set_position(sddc_ddc_t *h, uint64_t pos);
+/* Set the AGC's stream position (samples since the set; only its value mod SDDC_DDC_AGC_BLOCK decides
+ * where the blocks end), the envelopes left as they are: tests start a stream inside a block.
+ * SDDC_ERR_STATE: no AGC set. */
+int sddc_ddc_internal_chagc_set_position(sddc_ddc_t *h, uint64_t pos);
 /* demod_math.h's two routines as the CPU backend compiles them, on arrays of n values: out[i] =
  * angle(im[i], re[i]); (c[i], s[i]) = cos and sin of 2 pi words[i] / 2^32 (the accuracy sweeps of
  * tests/test_channel_demod_cpu.py; no handle, no device). */

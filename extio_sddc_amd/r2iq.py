@@ -157,6 +157,17 @@ def biquad(kind: int, f: float = 0.25, q: float = 0.7071067811865476) -> np.ndar
     return c
 
 
+AGC_BLOCK = 256                           # SDDC_DDC_AGC_BLOCK: the AGC's block length B
+
+
+def agc_decay(tau_samples: float) -> float:
+    """The AGC release factor d of a time constant of tau_samples samples: float32(exp(-1 / tau)),
+    1 - 2^-24 if that rounds to 1 (sddc_ddc_agc_decay)."""
+    d = ctypes.c_float()
+    check(_lib.load().sddc_ddc_agc_decay(float(tau_samples), ctypes.addressof(d)))
+    return float(d.value)
+
+
 def psd_to_dbfs(psd) -> np.ndarray:
     """R2iq.spectrum's output in dB relative to a full-scale real tone (amplitude 32768 reads
     32768^2 / 4 at its bin centre): 10 log10(4 psd / 32768^2); -inf where psd is 0."""
@@ -187,6 +198,7 @@ class R2iq:
         self._resamp = None  # (ntaps, up, down, nch) of setChannelResampler
         self._demod = None   # (nch, out_format) of setChannelDemodulator
         self._audio = None   # (nch, in_format, out_format) of setChannelAudioFilter
+        self._agc = None     # (nch, in_format, out_format) of setChannelAgc
 
     # -- lifecycle --------------------------------------------------------
     @property
@@ -716,6 +728,79 @@ class R2iq:
                 raise DDCError(-1, f"{name} has {t.numel()} samples, need {need}")
         check(self._L.sddc_ddc_channel_audio_filter_device(self._h, d_in.data_ptr(), nch, nsamp, in_stride,
                                                            d_out.data_ptr(), out_stride, _stream_handle(stream)))
+
+    # -- channel AGC ------------------------------------------------------------------
+    def setChannelAgc(self, params, in_format: int = AUDIO_F32, out_format: int = AUDIO_F32) -> None:
+        """The streaming peak AGC of channel_agc: params is float32 [nch, 3], per channel (T, d, F):
+        the target peak level (0: the channel is bypassed), the release factor per sample
+        (agc_decay) in [0, 1) and the envelope floor (the largest gain is T / F).  in_format /
+        out_format AUDIO_F32 or AUDIO_S16.  Every call zeroes the envelopes and the stream position.
+        params=None turns the stage off."""
+        if params is None or np.size(params) == 0:
+            check(self._L.sddc_ddc_set_channel_agc(self._h, None, 0, 0, 0))
+            self._agc = None
+            return
+        p = np.ascontiguousarray(np.asarray(params, np.float32))
+        if p.ndim != 2 or p.shape[1] != 3:
+            raise DDCError(-1, "params must be [nch, 3]")
+        check(self._L.sddc_ddc_set_channel_agc(self._h, p.ctypes.data, p.shape[0], int(in_format), int(out_format)))
+        self._agc = (p.shape[0], int(in_format), int(out_format))
+
+    def resetChannelAgc(self) -> None:
+        """Zero every channel's envelopes and the stream position: the next call starts a new stream."""
+        check(self._L.sddc_ddc_channel_agc_reset(self._h))
+
+    def channel_agc(self, x: np.ndarray, envelope: bool = False):
+        """The AGC on a host array: x is float32 (AUDIO_S16 in: int16) [nch, nsamp], any nsamp >= 1; a
+        single stream may drop the channel axis.  Returns float32 (AUDIO_S16 out: int16) [nch, nsamp],
+        with envelope=True also the float32 [nch] running envelopes after the last sample, and keeps
+        every channel's state for the next call."""
+        if self._agc is None:
+            raise DDCError(-4, "no channel AGC set")
+        nch, fin, fout = self._agc
+        x = np.asarray(x, np.int16 if fin == AUDIO_S16 else np.float32)
+        if x.ndim == 1:
+            x = x[None, :]
+        x = np.ascontiguousarray(x)
+        if x.ndim != 2 or x.shape[1] < 1:
+            raise DDCError(-1, "x must be [nch, nsamp] with nsamp >= 1")
+        nsamp = x.shape[1]
+        out = np.empty((x.shape[0], nsamp), np.int16 if fout == AUDIO_S16 else np.float32)
+        env = np.empty(x.shape[0], np.float32) if envelope else None
+        check(self._L.sddc_ddc_channel_agc_host(self._h, x.ctypes.data, x.shape[0], nsamp, nsamp, out.ctypes.data, nsamp,
+                                                None if env is None else env.ctypes.data))
+        return (out, env) if envelope else out
+
+    def channel_agc_device(self, d_in, nch: int, nsamp: int, in_stride: int, d_out, out_stride: int, d_env=None,
+                           stream=None) -> None:
+        """The AGC on the buffer channel_demodulate_device or channel_audio_filter_device wrote (the same
+        buffer, stride and format): d_in is a float32 (AUDIO_S16 in: int16) device tensor, channel c's
+        nsamp samples at c * in_stride; d_out float32 (AUDIO_S16 out: int16), channel c's outputs at
+        c * out_stride; the two must not overlap; d_env None or a float32 device tensor of nch values
+        that receives the running envelopes after the last sample.  Enqueued on `stream` like
+        process_device; the calls of one handle run in call order."""
+        import torch
+        if self._agc is None:
+            raise DDCError(-4, "no channel AGC set")
+        if nch < 1 or nsamp < 1:
+            raise DDCError(-1, "nch and nsamp must be >= 1")
+        if not (d_in.is_cuda and d_out.is_cuda and (d_env is None or d_env.is_cuda)):
+            raise DDCError(-1, "device path needs device tensors")
+        want = torch.int16 if self._agc[1] == AUDIO_S16 else torch.float32
+        want_out = torch.int16 if self._agc[2] == AUDIO_S16 else torch.float32
+        if d_in.dtype != want or d_out.dtype != want_out:
+            raise DDCError(-1, f"d_in must be {want} and d_out {want_out}")
+        if not (d_in.is_contiguous() and d_out.is_contiguous()):
+            raise DDCError(-1, "tensors must be contiguous")
+        for name, t, stride in (("d_in", d_in, in_stride), ("d_out", d_out, out_stride)):
+            need = (nch - 1) * stride + nsamp
+            if t.numel() < need:
+                raise DDCError(-1, f"{name} has {t.numel()} samples, need {need}")
+        if d_env is not None and (d_env.dtype != torch.float32 or not d_env.is_contiguous() or d_env.numel() < nch):
+            raise DDCError(-1, f"d_env must be a contiguous float32 tensor of at least {nch} values")
+        check(self._L.sddc_ddc_channel_agc_device(self._h, d_in.data_ptr(), nch, nsamp, in_stride, d_out.data_ptr(),
+                                                  out_stride, None if d_env is None else d_env.data_ptr(),
+                                                  _stream_handle(stream)))
 
 
 def _check_device_buffers(d_in, nblk, d_out, out_floats, fmt=0):

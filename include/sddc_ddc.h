@@ -58,7 +58,9 @@ extern "C" {
                                        still 3: + bfo_word, set_channel_demodulator, channel_demodulator_reset,
                                        channel_demodulate_device, channel_demodulate_host (new symbols only);
                                        still 3: + biquad, set_channel_audio_filter, channel_audio_filter_reset,
-                                       channel_audio_filter_device, channel_audio_filter_host (new symbols only) */
+                                       channel_audio_filter_device, channel_audio_filter_host (new symbols only);
+                                       still 3: + agc_decay, set_channel_agc, channel_agc_reset,
+                                       channel_agc_device, channel_agc_host (new symbols only) */
 
 #define SDDC_DDC_HALF_FFT   4096    /* halfFft               fft_mt_r2iq.h:18 */
 #define SDDC_DDC_FFTN       8192    /* FFTN_R_ADC            config.h:49 */
@@ -497,8 +499,8 @@ int sddc_ddc_channel_demodulate_host(sddc_ddc_t *h, const void *iq, int nch, siz
  * high-pass of a voice channel, a notch.  Each of nch real audio streams runs through its own cascade
  * of S = nsec (1..4, the same count for every channel) biquad sections; a section is five floats
  * (b0, b1, b2, a1, a2) with a0 = 1, in transposed direct form II; a channel that wants fewer sections
- * pads with (1, 0, 0, 0, 0), which passes finite values through exactly.  AGC is not here: it is
- * nonlinear, and the block form below is a property of linear recurrences.
+ * pads with (1, 0, 0, 0, 0), which passes finite values through exactly.  AGC is the next stage
+ * (sddc_ddc_channel_agc_* below): its recurrence is max-plus, not linear, and has a block form of its own.
  * Input: SDDC_DDC_AUDIO_F32, or SDDC_DDC_AUDIO_S16 read as (float)v; output F32, or S16 rounded as
  * the demodulator rounds it.  The demodulator's output feeds this stage directly: the same buffer,
  * stride and format.
@@ -587,6 +589,80 @@ int sddc_ddc_channel_audio_filter_device(sddc_ddc_t *h, const void *d_in, int nc
  * arithmetic header. */
 int sddc_ddc_channel_audio_filter_host(sddc_ddc_t *h, const void *in, int nch, size_t nsamp, size_t in_stride,
                                        void *out, size_t out_stride);
+
+/* ---- channel AGC: a streaming per-channel peak AGC on the device ---------------------------
+ * Level control between the demodulator (or the audio filter) and audio that can be played or fed to
+ * a codec: an AM or SSB channel at S9+40 and one at S3 leave the device at the same peak level.  A
+ * fast-attack, exponential-release peak AGC: the envelope e[n] = max(|x[n]|, d e[n-1]) and the output
+ * y[n] = T x[n] / max(e[n], F).  Channel c has three floats: T, the target peak level (T == 0: the
+ * channel is bypassed, y = x as it is), d, the release factor per sample (sddc_ddc_agc_decay), and F,
+ * the envelope floor: the largest gain is T / F.  What this AGC is NOT: there is no hang timer, no
+ * look-ahead and no attack smoothing (a new peak takes the gain down within its own sample); a hang
+ * needs a sliding-window maximum and is a later step.
+ * Input: SDDC_DDC_AUDIO_F32, or SDDC_DDC_AUDIO_S16 read as (float)v; output F32, or S16 rounded as the
+ * demodulator rounds it.  The demodulator's or the audio filter's buffer feeds this stage as it lies:
+ * the same buffer, stride and format.
+ * The definition, which both backends compute bit for bit (csrc/agc_math.h: *, / and comparisons are
+ * the correctly rounded float operations, nothing is contracted, no libm).  The recurrence above is a
+ * max-plus recurrence: the maps e -> max(m, k e) compose associatively, as affine maps do, so a block
+ * of B = SDDC_DDC_AGC_BLOCK samples collapses to a pair (m, k = d^B).  With dB = float(d^B), computed
+ * at set time (eight squarings of (double)d with plain, uncontracted *, then one rounding to float;
+ * it may underflow to 0), the magnitude a = |x| except that a NaN gives a = 0 and an infinity
+ * a = FLT_MAX, and step(a, e): t = d * e; e = (a > t) ? a : t, each channel has the entry envelope E
+ * of the current block, the running envelope R, the running envelope from a zero start Zr and one
+ * position n, the samples since the last set or reset, all zero then.  Per sample:
+ *     R = step(a, R);  Zr = step(a, Zr);  den = (R > F) ? R : F;  g = T / den;  y[n] = g * x
+ *     (a bypassed channel: y[n] = x);  n++;
+ *     if n is a multiple of B:  t = dB * E;  E = (Zr > t) ? Zr : t;  R = E;  Zr = 0.
+ * In exact arithmetic this is the plain recurrence.  In float it differs from it by roundings only,
+ * and a block's outputs depend on the earlier stream through E alone, so the device runs the blocks
+ * of a call in parallel.  The envelope runs for bypassed channels too: it is their signal meter.  The
+ * definition never mentions calls, grids or streams: an output sample and the envelope are
+ * BIT-IDENTICAL for any cut of the same samples into calls, for any grid and run length, on any
+ * stream, for a channel alone or among others, and between a GPU handle and a CPU handle (subnormal
+ * envelopes of a decay included: no FTZ / DAZ on either side).  A NaN sample leaves the envelope as it
+ * is and gives a NaN (S16: 0) at that sample only; an infinite sample sets the envelope to FLT_MAX.
+ * den >= |x|, so |y| <= T (1 + 2 u), u = 2^-24: with T <= 32767 / (1 + 2 u) (32767 is not, 32766 is)
+ * the stage cannot clip an S16 output.
+ * Accuracy against the float64 plain recurrence y64 on the same float32 parameters and samples:
+ * every candidate |x[t]| d^(n-t) of the maximum reaches R through at most B - 1 rounded multiplies in
+ * the zero-start pass of its own block, one multiply by dB per later boundary (one rounding, plus
+ * dB's own rounding) and at most B multiplies in n's block; max is monotone, so with
+ * K(n) = ceil((n + 1) / B)
+ *     |y[n] - y64[n]| <= 1.01 (2 B + 2 K(n) + 2) u |y64[n]|      (F32 out; S16 adds 1/2 and the clamp)
+ * while no envelope on the deciding path is subnormal, which F >= 2^-60 ensures for den.
+ * tools/channel_agc_model.py evaluates it.
+ * Validity, checked at set time: everything finite; T == 0 or 2^-60 <= T <= 2^60; 2^-60 <= F <= 2^60;
+ * 0 <= d < 1; anything else returns SDDC_ERR_ARG and sets nothing. */
+#define SDDC_DDC_AGC_BLOCK 256
+/* The release factor of a time constant of tau_samples samples: float(exp(-1 / tau_samples)), and
+ * 1 - 2^-24 if that rounds to 1.0f.  tau_samples <= 0, a value that is not finite or a null pointer
+ * returns SDDC_ERR_ARG.  Stateless. */
+int sddc_ddc_agc_decay(double tau_samples, float *decay);
+/* params: host array [nch][3] = (T, d, F); 1 <= nch <= SDDC_DDC_MAX_CHANNELS; in_format and out_format
+ * SDDC_DDC_AUDIO_*; a violation returns SDDC_ERR_ARG and sets nothing.  params NULL or nch == 0 turns
+ * the stage off and frees its state.  Every set call zeroes the envelopes and the position, and waits
+ * for the stage's launches in flight.  The state is independent of every other stage's. */
+int sddc_ddc_set_channel_agc(sddc_ddc_t *h, const float *params, int nch, int in_format, int out_format);
+/* zero every channel's envelopes and the position: the next call starts a new stream (SDDC_ERR_STATE:
+ * no AGC set) */
+int sddc_ddc_channel_agc_reset(sddc_ddc_t *h);
+/* GPU handles; enqueued on hip_stream, returns after launch.  Buffers, strides, alignment and
+ * 1 <= nsamp <= 2^40 as for sddc_ddc_channel_audio_filter_device; the input and the output must not
+ * overlap; nothing is written between the streams or outside them.  d_env: NULL, or nch device floats
+ * that receive R_c after the call's last sample: the unfloored envelope, an S-meter per channel, part
+ * of the bit-exact guarantee.  SDDC_ERR_STATE: no AGC set, another nch than the set one, a CPU handle.
+ * SDDC_ERR_ARG: nsamp == 0 or above 2^40, a bad stride or alignment, a null buffer.  A failed call
+ * changes no state.  The calls of one handle share the state and the position: they run one after the
+ * other in call order, whatever their streams.  A long call is processed in runs of a bounded number
+ * of blocks (the scratch of a run is one float per channel and block), which changes no output bit. */
+int sddc_ddc_channel_agc_device(sddc_ddc_t *h, const void *d_in, int nch, size_t nsamp, size_t in_stride, void *d_out,
+                                size_t out_stride, float *d_env, void *hip_stream);
+/* Host buffers, the same layouts; env NULL or nch floats.  GPU handle: copy in, kernels, copy back,
+ * synchronous; it advances the same device state as the device call.  CPU handle: the definition's
+ * loop through the same arithmetic header. */
+int sddc_ddc_channel_agc_host(sddc_ddc_t *h, const void *in, int nch, size_t nsamp, size_t in_stride, void *out,
+                              size_t out_stride, float *env);
 
 /* ---- ingest ---------------------------------------
  * Pin a caller-owned host region (hipHostRegister) so the host path DMAs blocks
