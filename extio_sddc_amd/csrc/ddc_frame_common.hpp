@@ -160,12 +160,16 @@ __device__ __forceinline__ void table_twiddle(float2 *a, const float2 *tbl, int 
 }
 
 // this thread's 16 int16 pairs of frame k of block blk: pair t + 256 r
-__device__ __forceinline__ void load_frame(const int *__restrict__ in32, int blk, int k, int (&x)[16])
+// (vo: the thread's byte offset 4 t, for a caller that holds it)
+__device__ __forceinline__ void load_frame(const int *__restrict__ in32, int blk, int k, int (&x)[16], unsigned vo)
 {
     const __amdgpu_buffer_rsrc_t rs = buf_rsrc(in32 + ((size_t)blk * BLOCK + (size_t)k * HOP) / 2);
-    const unsigned vo = 4u * threadIdx.x;
 #pragma unroll
     for (int r = 0; r < 16; r++) x[r] = buf_load4<SDDC_LD_AUX>(rs, vo, 4u * NT * r);
+}
+__device__ __forceinline__ void load_frame(const int *__restrict__ in32, int blk, int k, int (&x)[16])
+{
+    load_frame(in32, blk, k, x, 4u * threadIdx.x);
 }
 
 }  // namespace

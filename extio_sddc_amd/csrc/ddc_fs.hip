@@ -36,6 +36,11 @@
 // workgroups' measured end times, fs_split_controller.hpp; queue, work stealing: options), the
 // next frame's input prefetched into registers under inverse pass 1, all global memory through raw buffer instructions (scalar base
 // + lane offset), nt IQ stores.
+// The static schedule's frame loop takes its seven LDS lane bases from four packed registers built
+// once per launch (fs_bases.h) instead of re-deriving them in every pass: 1328 -> 1300 VALU per
+// wave-frame and 128 -> 120 VGPRs in the benchmark instance, about 2 us of a 201 us launch
+// (profiles/packed_bases).  Fusing wave 0's mirror selects into the DPP read (149 ->
+// 122 VALU in its split) measured neutral with and without the packed bases and is not here.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -44,7 +49,14 @@
 #include "ddc_queue.hpp"
 #include "ddc_stamps.hpp"
 #include "ddc_fs_perm.h"
+#include "fs_bases.h"
 #include "split_coeffs.h"
+
+// 1: a build whose static instances re-derive the LDS lane bases in every pass, as before the
+// packed bases (the comparison library of tests/test_gpu_fs_packed_bases.py and of A/B timing)
+#ifndef SDDC_FS_RECOMPUTED
+#define SDDC_FS_RECOMPUTED 0
+#endif
 
 namespace sddc {
 namespace {
@@ -88,6 +100,23 @@ __device__ __forceinline__ void split_v1(float2 &z, float2 zp, float r)
         : "v"(zp.x), "v"(zp.y), "v"(r));
 }
 
+// The packed lane bases (fs_bases.h) are LDS byte addresses: the address of an LDS object, and
+// the pointer at an address (the compiler follows the cast and emits ds_ instructions)
+typedef __attribute__((address_space(3))) float2 lds_float2;
+__device__ __forceinline__ unsigned lds_addr(const float2 *p)
+{
+    return (unsigned)(size_t)(const lds_float2 *)p;
+}
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ float2 *lds_at(unsigned a) { return (float2 *)(lds_float2 *)a; }
+#else
+__device__ __forceinline__ float2 *lds_at(unsigned) { return nullptr; }   // (the host pass only parses the kernel)
+#endif
+
+// a packed word made opaque to the compiler, in place (no instruction): what is unpacked from it
+// afterwards cannot be computed, or kept, ahead of this point
+__device__ __forceinline__ void fs_opaque(unsigned &w) { asm volatile("" : "+v"(w)); }
+
 // F = P V
 __device__ __forceinline__ float2 p_mul(float2 v, float2 q)
 {
@@ -127,14 +156,7 @@ constexpr int kQWave = 3;
 // holding forward pass 2's eight product twiddle powers in registers across frames (26 VALU per
 // wave-frame fewer, 128 VGPRs, spills in the NCO / CS16 instances) measured neutral (same files).
 constexpr int kFsPqAhead = 1;
-// fs_slot(t, 0): the F0 / I2 row of thread t
-__device__ __forceinline__ int fs_row_slot(int t) { return 272 * (t >> 4) + (t >= 128) + 34 * ((t & 15) >> 1) + (t & 1); }
-// fs_pair_lane: F1's and I1's thread t takes row u = 2 (t >> 5) + (t & 1) of each 16-row block,
-// column j = (t >> 1) & 15: its base slot fs_slot(u, j) = 34 (t >> 5) + (t & 31) = t + 2 (t >> 5)
-// (the block's 272 r + [r >= 8] is the immediate)
-__device__ __forceinline__ int fs_pair_row(int t) { return 2 * (t >> 5) + (t & 1); }
-__device__ __forceinline__ int fs_pair_col(int t) { return (t >> 1) & 15; }
-__device__ __forceinline__ int fs_pair_slot(int t) { return t + 2 * (t >> 5); }
+// fs_row_slot, fs_pair_row / _col / _slot, fs_col_slot, fs_tw_slot: fs_bases.h
 // The exchanges' LDS layout (round 6): row R (0..255), column j (0..15) at
 //   fs_slot(R, j) = 272 (R >> 4) + [R >= 128] + 34 ((R & 15) >> 1) + (R & 1) + 2 j:
 // rows 2i and 2i + 1 of a 16-row block interleave (even and odd slots) in a 32-slot run, the runs
@@ -155,12 +177,11 @@ __device__ __forceinline__ int fs_pair_slot(int t) { return t + 2 * (t >> 5); }
 // conflict-free too but 4 % slower: its input loads and IQ stores were no longer in lane order
 // (DESIGN.md §4.1, round 6).  tests/test_fs_model.py checks every exchange's delivery, the in-place
 // property and the bank keys.
-constexpr int kFsLds = 4352;
 // twiddle bases W^j (j < 256) at j + [j >= 128], W^{4j} kFsTw later: F2 reads them at its column
 // c = kFsPerm[t], whose key c + [c >= 128] the permutation keeps distinct mod 32 over 32 lanes
 // (tools/fs_perm.py), I2 at t; both ds_read_b64 and conflict-free.  (Unpadded, the lane pairs
 // c, 256 - c with c = 0 mod 16 hit one bank.)
-constexpr int kFsTw = NT + 1;
+static_assert(kFsTw == NT + 1 && kFsTwl == 15 * 16, "fs_bases.h");
 
 // the frame schedules (ddc_queue.hpp): the slot-weighted static split alone (the default), the
 // static prefix + dynamic queue (round 3/4), work stealing over the static split (round 5)
@@ -235,9 +256,27 @@ __global__ __launch_bounds__(NT, 4) void r2iq_fs_kernel(
     }
     int f = s_next;
     int blk = f / FRAMES, k = f - blk * FRAMES;
+    // PK: the static schedule's frame loop takes its LDS lane bases from four packed registers
+    // (fs_bases.h).  The queue and stealing instances, and every instance of a
+    // -DSDDC_FS_RECOMPUTED=1 build (the comparison library of the tests and A/Bs, not the
+    // product), re-derive them from the thread index and column in every pass.
+    constexpr bool PK = SCHED == kSchedStatic && SDDC_FS_RECOMPUTED == 0;
+    // a packed half is 16 bits: every LDS byte address of the workgroup has to fit
+    static_assert(sizeof(float2) * (kFsLds + kFsTwl + 2 * kFsTw) + sizeof(int) <= 65536, "fs_bases.h: 16-bit LDS addresses");
     const int col_ = kFsPerm[tid];
+    // the packed lane bases (fs_bases.h): built once, made opaque again at every use in the loop
+    // so that the compiler neither unpacks them ahead of it nor keeps a half live across a pass
+    unsigned b0 = 0u, b1 = 0u, b2 = 0u, b3 = 0u;
+    if constexpr (PK) {
+        const FsBases fb = fs_bases_pack(tid, col_, lds_addr(lds), lds_addr(twl), lds_addr(wtab));
+        b0 = fb.p[0];
+        b1 = fb.p[1];
+        b2 = fb.p[2];
+        b3 = fb.p[3];
+    }
     const int qt = (tunebin >> 2) & 3;   // (tb mod 16) / 4: the output quarter turns
     const bool w0 = __builtin_amdgcn_readfirstlane(tid >> 6) == 0;   // the wave holding columns 0, 128
+    const int widx = __builtin_amdgcn_readfirstlane(tid >> 6);
     // The frame loop runs in two phases.  Phase A: frames of the workgroup's own range whose next
     // frame and the one after it are private too (StaticSchedule: all of them), the next frame
     // f + 1, known to every wave, no schedule state.  Phase B: the rest, with the schedule object
@@ -303,8 +342,8 @@ __global__ __launch_bounds__(NT, 4) void r2iq_fs_kernel(
         // hoists every loop-invariant LDS address out of the frame loop and spills them
         int z = 0;
         asm volatile("" : "+s"(z));
-        const int t = tid + z;
-        const int c = col_ + z;
+        const int t = PK ? 0 : tid + z;
+        const int c = PK ? 0 : col_ + z;
         const int oblk = blk * 8 * HALF;
         const int kc = k;
         // ---- F0 (R16, NS1): convert + DFT16 from registers ----
@@ -326,7 +365,13 @@ __global__ __launch_bounds__(NT, 4) void r2iq_fs_kernel(
         // no barrier: this thread's row is exactly what it read in the previous frame's inverse
         // pass 2 (every exchange writes in place of its own reads)
         {
-            float2 *const row = lds + fs_row_slot(t);
+            float2 *row;
+            if constexpr (PK) {
+                fs_opaque(b0);
+                row = lds_at(fs_lo(b0));
+            } else {
+                row = lds + fs_row_slot(t);
+            }
 #pragma unroll
             for (int r = 0; r < 16; r++) row[2 * r] = v[r];
         }
@@ -335,15 +380,32 @@ __global__ __launch_bounds__(NT, 4) void r2iq_fs_kernel(
         // rows 16 r + u, column j of the thread's pair lane (u, j) (fs_pair_lane)
         {
             float2 a[16];
-            const float2 *const col = lds + fs_pair_slot(t);
+            const float2 *col;
+            if constexpr (PK) {
+                fs_opaque(b0);
+                col = lds_at(fs_hi(b0));
+            } else {
+                col = lds + fs_pair_slot(t);
+            }
 #pragma unroll
             for (int r = 0; r < 16; r++) XRD(a[r], col[272 * r + (r >= 8)]);
-            table_twiddle<-1, true>(a, twl, 16, fs_pair_col(t));
+            if constexpr (PK) {
+                fs_opaque(b2);
+                table_twiddle<-1, true>(a, lds_at(fs_hi(b2)), 16, 0);
+            } else {
+                table_twiddle<-1, true>(a, twl, 16, fs_pair_col(t));
+            }
             dft16<-1>(a, v);
         }
         {
             // in place of the reads (no barrier)
-            float2 *const col = lds + fs_pair_slot(t);
+            float2 *col;
+            if constexpr (PK) {
+                fs_opaque(b0);
+                col = lds_at(fs_hi(b0));
+            } else {
+                col = lds + fs_pair_slot(t);
+            }
 #pragma unroll
             for (int r = 0; r < 16; r++) col[272 * r + (r >= 8)] = v[r];
         }
@@ -357,7 +419,13 @@ __global__ __launch_bounds__(NT, 4) void r2iq_fs_kernel(
         // for every pair right after issuing it).  Issuing the first pair after the register-held
         // ones before F2 instead measured -2.4 to +0.9 % (fs_first_uncached_p_before_f2_NEUTRAL.txt).
         const __amdgpu_buffer_rsrc_t rpq = buf_rsrc(pqf + z);
-        const unsigned t16 = 16u * (unsigned)t;
+        unsigned t16;
+        if constexpr (PK) {
+            fs_opaque(b3);
+            t16 = fs_t16(b3);
+        } else {
+            t16 = 16u * (unsigned)t;
+        }
         float2 qa[8], qb[8];
         // pair p's P (rows p and 15 - p side by side, build_fs_tables_kernel): one 16-byte load,
         // or 8 bytes when a row is zero; the first CPP pairs from registers
@@ -391,11 +459,22 @@ __global__ __launch_bounds__(NT, 4) void r2iq_fs_kernel(
             // F1 output c >> 4 of its pair lanes (r, c & 15): rows 16 (c >> 4) + r, column c & 15
             // at 272 (c >> 4) + [c >= 128] + 2 (c & 15) + 34 (r >> 1) + (r & 1): base + immediate,
             // conflict-free with kFsPerm (tools/fs_perm.py)
-            const float2 *const cb = lds + 272 * (c >> 4) + (c >= 128) + 2 * (c & 15);
+            const float2 *cb, *wc;
+            if constexpr (PK) {
+                fs_opaque(b1);
+                cb = lds_at(fs_lo(b1));
+            } else {
+                cb = lds + fs_col_slot(c);
+            }
 #pragma unroll
             for (int r = 0; r < 16; r++) XRD(a[r], cb[34 * (r >> 1) + (r & 1)]);
-            const int cw = c + (c >= 128);
-            const float2 fw1 = wtab[cw], fw4 = wtab[kFsTw + cw];   // W^c, W^{4c}
+            if constexpr (PK) {
+                fs_opaque(b1);
+                wc = lds_at(fs_hi(b1));
+            } else {
+                wc = wtab + fs_tw_slot(c);
+            }
+            const float2 fw1 = wc[0], fw4 = wc[kFsTw];   // W^c, W^{4c}
             twiddle_rec16<-1>(a, fw1, fw4);
             dft16<-1>(a, v);
         }
@@ -407,7 +486,13 @@ __global__ __launch_bounds__(NT, 4) void r2iq_fs_kernel(
                 // wave 0: lanes 0 (column 0: mirror of register k is its own (16 - k) mod 16) and
                 // 1 (column 128: its own 15 - k) are self-mirrored.  Bin 2048 (lane 0, register 8)
                 // has P = 0 (r infinite): its table entry holds Q, and F = Q conj(Z) there.
-                const int lane = t & 63;
+                int lane;
+                if constexpr (PK) {
+                    fs_opaque(b3);
+                    lane = (int)fs_lane(b3);
+                } else {
+                    lane = t & 63;
+                }
 #pragma unroll
                 for (int p = 0; p < 8; p++) {
                     if (p + kFsPqAhead < 8) {
@@ -458,7 +543,8 @@ __global__ __launch_bounds__(NT, 4) void r2iq_fs_kernel(
             // and every update went through a copy (16 v_mov per wave-frame).  Without zero rows
             // the two-if form spills 2-4 VGPRs, so ZR = 0 keeps the if / else.
             if constexpr (ZR != 0) {
-                int wv = __builtin_amdgcn_readfirstlane(t >> 6);
+                // (PK: t is not held; the wave index is a scalar of the launch)
+                int wv = PK ? widx : __builtin_amdgcn_readfirstlane(t >> 6);
                 asm volatile("" : "+s"(wv));
                 if (w0) split_w0();
                 if (wv != 0) split_generic();
@@ -472,7 +558,13 @@ __global__ __launch_bounds__(NT, 4) void r2iq_fs_kernel(
             // in place of this thread's F2 reads (no barrier): output r at row 16 (c >> 4) + r
             int c1 = c;
             asm volatile("" : "+v"(c1));
-            float2 *const cb = lds + 272 * (c1 >> 4) + (c1 >= 128) + 2 * (c1 & 15);
+            float2 *cb;
+            if constexpr (PK) {
+                fs_opaque(b1);
+                cb = lds_at(fs_lo(b1));
+            } else {
+                cb = lds + fs_col_slot(c1);
+            }
 #pragma unroll
             for (int r = 0; r < 16; r++) cb[34 * (r >> 1) + (r & 1)] = u[r];
         }
@@ -505,7 +597,13 @@ __global__ __launch_bounds__(NT, 4) void r2iq_fs_kernel(
             float2 a[16];
             // I0 output s of columns 16 r + cl, for the pair lane (s, cl) = (u, j) of this
             // thread (fs_pair_lane): rows 16 r + s, column cl, the slots F1 used
-            const float2 *const ib = lds + fs_pair_slot(t);
+            const float2 *ib;
+            if constexpr (PK) {
+                fs_opaque(b0);
+                ib = lds_at(fs_hi(b0));
+            } else {
+                ib = lds + fs_pair_slot(t);
+            }
 #pragma unroll
             for (int r = 0; r < 16; r++) XRD(a[r], ib[272 * r + (r >= 8)]);
             // the next frame's number is read behind the data reads (its LDS round trip under
@@ -516,14 +614,24 @@ __global__ __launch_bounds__(NT, 4) void r2iq_fs_kernel(
             if (fn >= 0) {
                 blk = fn / FRAMES;
                 k = fn - blk * FRAMES;
-                load_frame(in32, blk, k, x);
+                if constexpr (PK) {
+                    fs_opaque(b3);
+                    load_frame(in32, blk, k, x, fs_t4(b3));
+                } else {
+                    load_frame(in32, blk, k, x);
+                }
             }
             // the ticket for the frame after the next one, when that one is dynamic: behind this
             // frame's last loads (vmcnt counts in issue order: taken at inverse pass 0, the wait
             // for I2's lane factors included the atomic); read at the next frame's top
             if constexpr (PB)
                 if (qw) fsch.take();
-            table_twiddle<+1, true>(a, twl, 16, fs_pair_row(t));
+            if constexpr (PK) {
+                fs_opaque(b3);
+                table_twiddle<+1, true>(a, lds_at(fs_lo(b3)), 16, 0);
+            } else {
+                table_twiddle<+1, true>(a, twl, 16, fs_pair_row(t));
+            }
             dft16<+1>(a, u);
         }
         {
@@ -531,7 +639,13 @@ __global__ __launch_bounds__(NT, 4) void r2iq_fs_kernel(
             // t (else kept live through the pass): output g at row 16 g + s, column cl
             int t1 = t;
             asm volatile("" : "+v"(t1));
-            float2 *const ib = lds + fs_pair_slot(t1);
+            float2 *ib;
+            if constexpr (PK) {
+                fs_opaque(b0);
+                ib = lds_at(fs_hi(b0));
+            } else {
+                ib = lds + fs_pair_slot(t1);
+            }
 #pragma unroll
             for (int r = 0; r < 16; r++) ib[272 * r + (r >= 8)] = u[r];
         }
@@ -541,19 +655,35 @@ __global__ __launch_bounds__(NT, 4) void r2iq_fs_kernel(
             float2 a[16];
             // row t (I1 outputs t >> 4 of its pair lanes (t & 15, r)): the next frame's F0 row of
             // this thread
-            const float2 *const rb = lds + fs_row_slot(t);
+            const float2 *rb, *wt;
+            if constexpr (PK) {
+                fs_opaque(b0);
+                rb = lds_at(fs_lo(b0));
+            } else {
+                rb = lds + fs_row_slot(t);
+            }
 #pragma unroll
             for (int r = 0; r < 16; r++) XRD(a[r], rb[2 * r]);
-            const int tw = t + (t >= 128);
-            const float2 rw1 = wtab[tw], rw4 = wtab[kFsTw + tw];   // W^t, W^{4t}
+            if constexpr (PK) {
+                fs_opaque(b2);
+                wt = lds_at(fs_lo(b2));
+            } else {
+                wt = wtab + fs_tw_slot(t);
+            }
+            const float2 rw1 = wt[0], rw4 = wt[kFsTw];   // W^t, W^{4t}
             twiddle_g16<+1>(a, g0, g1, g4, rw1, rw4);
             dft16<+1>(a, u);
             const int fb = oblk + emit_base<HALF>(kc);
+            int te = t;
+            if constexpr (PK) {
+                fs_opaque(b3);
+                te = (int)fs_t(b3);
+            }
             switch (qt) {
-            case 0: emit_frame_q<0, LSB, NCO, CS16>(out, fb, kc, t, u, oa, nco); break;
-            case 1: emit_frame_q<1, LSB, NCO, CS16>(out, fb, kc, t, u, oa, nco); break;
-            case 2: emit_frame_q<2, LSB, NCO, CS16>(out, fb, kc, t, u, oa, nco); break;
-            default: emit_frame_q<3, LSB, NCO, CS16>(out, fb, kc, t, u, oa, nco); break;
+            case 0: emit_frame_q<0, LSB, NCO, CS16>(out, fb, kc, te, u, oa, nco); break;
+            case 1: emit_frame_q<1, LSB, NCO, CS16>(out, fb, kc, te, u, oa, nco); break;
+            case 2: emit_frame_q<2, LSB, NCO, CS16>(out, fb, kc, te, u, oa, nco); break;
+            default: emit_frame_q<3, LSB, NCO, CS16>(out, fb, kc, te, u, oa, nco); break;
             }
         }
         if constexpr (SCHED == kSchedSteal) {

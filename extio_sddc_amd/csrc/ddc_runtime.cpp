@@ -87,14 +87,32 @@ static_assert(SDDC_DDC_MAX_CHANNELS * kChNcoBlockBytes <= kChNcoTableCap, "one b
 // staging buffer, the channel tune bins, the channel scratch rows).  The C ABI accepts any
 // stream per call, so before a table is rewritten the writing stream waits for the last launch
 // of EVERY stream that may still read it, not only the most recent one.
+//
+// lazy (the single-channel launches' set, sddc_ddc::readers, only): a launch only notes that its
+// stream has work the event does not cover yet (pending), and the event is recorded on that stream
+// when somebody is about to wait for it.  An event recorded later covers a superset of the
+// launches, so every wait orders at least what it did, and a stream that is the handle's only one
+// never gets an event marker between its kernels: a steady-state call enqueues its kernel and
+// nothing else.  The record happens whether or not the stream's work has completed, at the latest
+// in the handle's destroy, so a stream given to sddc_ddc_process_device must stay valid until the
+// handle is destroyed (include/sddc_ddc.h).  Every other set records at each launch.
 struct Readers {
-    std::vector<std::pair<hipStream_t, hipEvent_t>> v;
+    struct Entry {
+        hipStream_t first;
+        hipEvent_t second;
+        bool pending;   // launches on `first` since `second` was recorded
+    };
+    std::vector<Entry> v;
+    bool lazy = false;   // true: sddc_ddc::readers (SDDC_DDC_PARAM_LAZY_RECORD = 0 turns it off, A/B)
 
     // after a launch on s that reads the tables
     hipError_t record(hipStream_t s)
     {
         for (auto &p : v)
-            if (p.first == s) return hipEventRecord(p.second, s);
+            if (p.first == s) {
+                p.pending = true;
+                return lazy ? hipSuccess : flush(p);
+            }
         if (v.size() >= 16) {   // bound the set: wait for all, forget them
             hipError_t e = sync();
             if (e != hipSuccess) return e;
@@ -103,36 +121,54 @@ struct Readers {
         hipEvent_t ev = nullptr;
         hipError_t e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
         if (e != hipSuccess) return e;
-        v.emplace_back(s, ev);
-        return hipEventRecord(ev, s);
+        v.push_back(Entry{s, ev, true});
+        return lazy ? hipSuccess : flush(v.back());
+    }
+    // the entry's event covers every launch noted so far
+    static hipError_t flush(Entry &p)
+    {
+        if (!p.pending) return hipSuccess;
+        hipError_t e = hipEventRecord(p.second, p.first);
+        if (e == hipSuccess) p.pending = false;
+        return e;
     }
     // stream s (about to rewrite a table) waits for every other reader's last launch
-    hipError_t order_before(hipStream_t s) const
+    hipError_t order_before(hipStream_t s)
     {
-        for (const auto &p : v)
+        for (auto &p : v)
             if (p.first != s) {
-                hipError_t e = hipStreamWaitEvent(s, p.second, 0);
+                hipError_t e = flush(p);
+                if (e == hipSuccess) e = hipStreamWaitEvent(s, p.second, 0);
                 if (e != hipSuccess) return e;
             }
         return hipSuccess;
     }
-    // stream s waits for the last recorded launch on stream `other` (nothing to do when other is
-    // s, or when `other` has no entry: entries are dropped only after a host sync of all of them)
-    hipError_t order_after(hipStream_t other, hipStream_t s) const
+    // stream s waits for the last launch on stream `other` (nothing to do when other is s, or
+    // when `other` has no entry: entries are dropped only after a host sync of all of them)
+    hipError_t order_after(hipStream_t other, hipStream_t s)
     {
         if (other == s) return hipSuccess;
-        for (const auto &p : v)
-            if (p.first == other) return hipStreamWaitEvent(s, p.second, 0);
+        for (auto &p : v)
+            if (p.first == other) {
+                hipError_t e = flush(p);
+                return e == hipSuccess ? hipStreamWaitEvent(s, p.second, 0) : e;
+            }
         return hipSuccess;
     }
-    // the host waits for every reader (before a synchronous copy or a free)
-    hipError_t sync() const
+    // the host waits for every reader (before a synchronous copy or a free).  An entry that fails
+    // (a stream that is no longer valid cannot take its pending record) does not end the wait:
+    // its event is waited for as last recorded, the remaining entries follow, and the first error
+    // is returned.
+    hipError_t sync()
     {
-        for (const auto &p : v) {
-            hipError_t e = hipEventSynchronize(p.second);
-            if (e != hipSuccess) return e;
+        hipError_t first = hipSuccess;
+        for (auto &p : v) {
+            hipError_t e = flush(p);
+            const hipError_t es = hipEventSynchronize(p.second);
+            if (e == hipSuccess) e = es;
+            if (e != hipSuccess && first == hipSuccess) first = e;
         }
-        return hipSuccess;
+        return first;
     }
     void clear()
     {
@@ -457,7 +493,7 @@ struct sddc_ddc {
     } fsa;
     bool q_used[kQueueSlots] = {};
     bool q_dirty[kQueueSlots] = {};
-    Readers readers;
+    Readers readers{{}, true};   // lazy: no event marker between the single-channel launches of one stream
 
     // fused fine-tune NCO: host chain + per-launch [T | lane starts] staged through a
     // pinned 3-slot ring into d_nco (stream-ordered copy before each launch)
@@ -1402,6 +1438,9 @@ int sddc_ddc_internal_set_param(sddc_ddc_t *h, int param, int value)
         return SDDC_OK;
     case SDDC_DDC_PARAM_FS_ZERO_ROWS:
         h->fs_sched.zr = value != 0;
+        return SDDC_OK;
+    case SDDC_DDC_PARAM_LAZY_RECORD:
+        h->readers.lazy = value != 0;
         return SDDC_OK;
     case SDDC_DDC_PARAM_FS_SLOT_WEIGHTS: {
         for (int k = 0; k < 4 && value != 0; k++) {

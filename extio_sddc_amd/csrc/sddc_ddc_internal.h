@@ -89,6 +89,12 @@ extern "C" {
  * for the audio filter; 0: the default (2048).  The run length changes no output bit (tests). */
 #define SDDC_DDC_PARAM_CHAGC_RUN_BLOCKS 19
 
+/* SDDC_DDC_PARAM_LAZY_RECORD != 0 (default 1): a single-channel launch (sddc_ddc_process_device and
+ * the host path's launches) notes its stream and records the stream's event only when another
+ * stream or the host is about to wait for it; 0: an event record after every launch, as the other
+ * entry points do (A/B of the gap between consecutive dispatches). */
+#define SDDC_DDC_PARAM_LAZY_RECORD 20
+
 int sddc_ddc_internal_set_param(sddc_ddc_t *h, int param, int value);
 /* A given table of n relative shares (n = the d = 0 kernel's full-residency grid, 4 x CUs) used as
  * it is, without clamps or measurements, until n = 0 clears it (tests). */

@@ -189,7 +189,9 @@ int sddc_ddc_set_output_format(sddc_ddc_t *h, int format, float cs16_scale);
  * complex samples in the output format (CF32: float (I,Q), 8-byte aligned;
  * CS16: int16 (I,Q), 4-byte aligned), in stream order.  Uses the handle's
  * d / sideband / rand / tunebin.  Enqueued on `hip_stream` (a hipStream_t;
- * NULL = default stream); returns after launch. */
+ * NULL = default stream); returns after launch.  A stream given to a call must
+ * stay valid until the handle is destroyed: a later call on another stream (a
+ * new tune bin, say) or the destroy orders itself after the stream's last call. */
 int sddc_ddc_process_device(sddc_ddc_t *h, const int16_t *d_in, int nblk,
                             void *d_out, void *hip_stream);
 
