@@ -87,6 +87,11 @@ SIGNATURES = {
     "sddc_ddc_channel_agc_reset": (_I, [_P]),
     "sddc_ddc_channel_agc_device": (_I, [_P, _P, _I, _SZ, _SZ, _P, _SZ, _P, _P]),
     "sddc_ddc_channel_agc_host": (_I, [_P, _P, _I, _SZ, _SZ, _P, _SZ, _P]),
+    "sddc_ddc_blanker_threshold": (_I, [ctypes.c_double, _P]),
+    "sddc_ddc_set_channel_blanker": (_I, [_P, _P, _I, _I, _I, _I, _I]),
+    "sddc_ddc_channel_blanker_reset": (_I, [_P]),
+    "sddc_ddc_channel_blank_device": (_I, [_P, _P, _I, _SZ, _SZ, _P, _SZ, _P, _P]),
+    "sddc_ddc_channel_blank_host": (_I, [_P, _P, _I, _SZ, _SZ, _P, _SZ, _P]),
     "sddc_ddc_register_host": (_I, [_P, _P, _SZ]),
     "sddc_ddc_unregister_host": (_I, [_P, _P]),
     # include/sddc_fft.h

@@ -322,7 +322,8 @@ void R2iq::channel_spectrum(const void *iq, bool cs16, int nch, size_t stride, i
 
 // The channel stream stages (sddc_ddc_channel_{decimate,resample}_host on a CPU handle) share three
 // steps.  split_stream: per channel the stream [tail | the call's samples] is split into I and Q
-// rows.  dot_iq: an output is the dot product of n reversed taps with n consecutive values of the
+// rows.  dot_iq (the resampler; the decimator's dot_iq_phases follows the device's order instead): an
+// output is the dot product of n reversed taps with n consecutive values of the
 // rows: eight lane sums of explicit FMAs over k = 8 i + lane, added in a fixed tree, then the last
 // n mod 8 taps one by one.  keep_tail: the last H values of the rows are the next call's tail.
 // The order depends on the tap index alone, so any cut of a stream into calls gives the same bits.
@@ -383,7 +384,24 @@ static void keep_tail(const float *xr, const float *xi, size_t nsamp, size_t H, 
 }
 
 // The channel decimator: output m is the dot product of the reversed taps g[k] = h[L - k] with the
-// ntaps values from sample m R on.
+// ntaps values w[k] from sample m R on, added in the device kernel's order (ddc_channel_decimate.hip):
+// with k = q R + r, a[q mod 4] = fma(g[k], w[k], a[q mod 4]) for r = 0 .. R - 1, q = 0, 1, ..., and
+// y = (a0 + a1) + (a2 + a3).  The same correctly rounded operations on the same floats: a CPU handle
+// and a GPU handle produce the same bits.
+static inline void dot_iq_phases(const float *g, const float *pr, const float *pi, int n, int R, float *y)
+{
+    float ar[4] = {0.f, 0.f, 0.f, 0.f}, ai[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int r = 0; r < R && r < n; r++) {
+        int q = 0;
+        for (int k = r; k < n; k += R, q++) {
+            ar[q & 3] = std::fmaf(g[k], pr[k], ar[q & 3]);
+            ai[q & 3] = std::fmaf(g[k], pi[k], ai[q & 3]);
+        }
+    }
+    y[0] = (ar[0] + ar[1]) + (ar[2] + ar[3]);
+    y[1] = (ai[0] + ai[1]) + (ai[2] + ai[3]);
+}
+
 void R2iq::channel_decimate(const void *iq, bool cs16, float inv_s, int nch, size_t nsamp, size_t in_stride,
                             const float *taps, int ntaps, int R, float *tail, float *out, size_t out_stride)
 {
@@ -396,7 +414,7 @@ void R2iq::channel_decimate(const void *iq, bool cs16, float inv_s, int nch, siz
                      xr.data(), xi.data());
         float *y = out + (size_t)c * out_stride;
         for (size_t m = 0; m < nout; m++)
-            dot_iq(g.data(), xr.data() + m * (size_t)R, xi.data() + m * (size_t)R, ntaps, y + 2 * m);
+            dot_iq_phases(g.data(), xr.data() + m * (size_t)R, xi.data() + m * (size_t)R, ntaps, R, y + 2 * m);
         keep_tail(xr.data(), xi.data(), nsamp, L, tl);
     }
 }
@@ -561,6 +579,64 @@ void R2iq::channel_agc(const void *in, bool in16, int nch, size_t nsamp, size_t 
         st[1] = R;
         st[2] = Zr;
         if (env) env[c] = R;
+    }
+}
+
+// The channel noise blanker: blanker_math.h's stream, sample by sample.
+void R2iq::channel_blank(const void *in, bool cs16, int nch, size_t nsamp, size_t in_stride, const float *par, int guard,
+                         int ref_blocks, int ref_mode, uint64_t pos, BlankerChannel *state, void *out, size_t out_stride,
+                         uint32_t *count)
+{
+    using namespace blank;
+    const int B = kBlankBlock, g = guard, M = ref_blocks;
+    const size_t words = cs16 ? 1 : 2;   // 32-bit words per stored sample
+    for (int c = 0; c < nch; c++) {
+        const uint32_t *x = static_cast<const uint32_t *>(in) + (size_t)c * in_stride / (cs16 ? 2 : 1);
+        uint32_t *y = static_cast<uint32_t *>(out) + (size_t)c * out_stride / (cs16 ? 2 : 1);
+        const float thr = par[2 * c], qmin = par[2 * c + 1];
+        BlankerChannel &st = state[c];
+        uint64_t k = pos / (uint64_t)B;
+        int b = (int)(pos % (uint64_t)B);
+        int n = k < (uint64_t)M ? (int)k : M;
+        auto threshold = [&]() { return n > 0 ? blank_threshold(thr, blank_reference(st.pw + kBlankMaxRef - n, n, ref_mode), qmin) : 0.f; };
+        float t = threshold();
+        uint32_t cnt = 0;
+        for (size_t i = 0; i < nsamp; i++) {
+            uint32_t w[2] = {x[i * words], cs16 ? 0u : x[i * words + 1]};
+            float fi, fq;
+            if (cs16) {
+                fi = (float)(int16_t)(w[0] & 0xffffu);
+                fq = (float)(int16_t)(w[0] >> 16);
+            } else {
+                __builtin_memcpy(&fi, &w[0], 4);
+                __builtin_memcpy(&fq, &w[1], 4);
+            }
+            const float q = blank_power(fi, fq);
+            st.q[b] = blank_finite(q) ? q : 0.f;
+            const bool hit = thr > 0.f && blank_hit(q, t, n);
+            st.since = hit ? 0u : (st.since < kBlankNoHit ? st.since + 1 : kBlankNoHit);
+            const bool blanked = st.since <= (uint32_t)(2 * g);
+            uint32_t d[2] = {w[0], w[1]};
+            if (g > 0) {   // the slot of x[i - g] is the one x[i] goes into
+                uint32_t *slot = st.hist + (size_t)((pos + i) % (uint64_t)g) * words;
+                for (size_t j = 0; j < words; j++) {
+                    d[j] = slot[j];
+                    slot[j] = w[j];
+                }
+            }
+            for (size_t j = 0; j < words; j++) y[i * words + j] = blanked ? 0u : d[j];
+            if (blanked && pos + i >= (uint64_t)g) cnt++;
+            if (++b == B) {
+                const float p = blank_tree(st.q);
+                for (int j = 0; j + 1 < kBlankMaxRef; j++) st.pw[j] = st.pw[j + 1];
+                st.pw[kBlankMaxRef - 1] = p;
+                b = 0;
+                k++;
+                n = k < (uint64_t)M ? (int)k : M;
+                t = threshold();
+            }
+        }
+        if (count) count[c] = cnt;
     }
 }
 

@@ -25,6 +25,7 @@
 
 #include "../agc_math.h"
 #include "../audio_iir_math.h"
+#include "../blanker_math.h"
 #include "../demod_math.h"
 #include "fft_avx2.hpp"
 
@@ -109,6 +110,21 @@ public:
     // after the call's last sample.
     static void channel_agc(const void *in, bool in16, int nch, size_t nsamp, size_t in_stride, const float *par,
                             unsigned block_pos, float *state, void *out, bool out16, size_t out_stride, float *env);
+    // The channel noise blanker (sddc_ddc.h, sddc_ddc_channel_blank_host; blanker_math.h): the definition's
+    // loop, sample by sample.  Channel c's nsamp IQ samples (float pairs, or int16 pairs when cs16) at in +
+    // c * in_stride components, its outputs in the same format at out + c * out_stride components.  par:
+    // [nch][2] = (thr, qmin); pos: the stream index of the call's first sample; state: [nch], before the
+    // call and replaced by the one after it; count: null, or [nch] blanked outputs of this call.
+    struct BlankerChannel {
+        float pw[blank::kBlankMaxRef] = {};       // the last block powers, the newest one last
+        float q[blank::kBlankBlock] = {};         // the unfinished block's q values, non-finite ones as 0
+        uint32_t hist[2 * blank::kBlankMaxGuard] = {};   // ring of the last g stored samples (CS16: one word each)
+        uint32_t since = kBlankNoHit;             // samples since the last hit, saturating
+    };
+    static constexpr uint32_t kBlankNoHit = 1u << 20;
+    static void channel_blank(const void *in, bool cs16, int nch, size_t nsamp, size_t in_stride, const float *par,
+                              int guard, int ref_blocks, int ref_mode, uint64_t pos, BlankerChannel *state, void *out,
+                              size_t out_stride, uint32_t *count);
     // demod_math.h's routines on arrays (the accuracy sweeps of tests/test_channel_demod_cpu.py)
     static void demod_angle_n(const float *im, const float *re, size_t n, float *out);
     static void demod_sincos_n(const uint32_t *words, size_t n, float *c, float *s);

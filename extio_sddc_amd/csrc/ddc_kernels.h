@@ -298,6 +298,21 @@ hipError_t launch_channel_agc(const KernelTables &t, const void *d_in, int in_s1
                               float *d_scratch, void *d_out, int out_s16, size_t out_stride, float *d_env, int max_wgs,
                               int device, hipStream_t s);
 
+// Channel noise blanker (ddc_channel_blank.hip, sddc_ddc_channel_blank_device): one call of the block-form
+// impulse blanker (blanker_math.h) over nch IQ streams laid out as for the channel decimator (strides in
+// components), CF32 or CS16 in and out.  pos: the stream index of the call's first sample; nsamp at most
+// kBlankMaxLaunch (the runtime cuts longer calls).  d_par: [nch][2] floats (thr, qmin); d_state_in /
+// d_state_out: [nch][kBlankStateWords] words before / after the call (two buffers); d_count: null, or
+// [nch] counters that the caller has zeroed, to which the call adds its blanked outputs.  Two launches on
+// s; max_wgs > 0 caps their grids and run_blocks > 0 sets the blocks per wave (tests; 0: chosen from the
+// size).  The caller has checked the strides.
+constexpr int kBlankStateWords = 404;
+constexpr size_t kBlankMaxLaunch = (size_t)1 << 28;
+hipError_t launch_channel_blank(const KernelTables &t, const void *d_iq, int cs16, int nch, size_t nsamp, size_t in_stride,
+                                uint64_t pos, const float *d_par, int guard, int ref_blocks, int ref_mode,
+                                const uint32_t *d_state_in, uint32_t *d_state_out, void *d_out, size_t out_stride,
+                                uint32_t *d_count, int max_wgs, int run_blocks, int device, hipStream_t s);
+
 // batched FFTs (fft_batch.hip, include/sddc_fft.h); fft_prepare fills the device's twiddle
 // table once (synchronises s the first time)
 hipError_t fft_prepare(hipStream_t s);

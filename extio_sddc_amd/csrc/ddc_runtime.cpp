@@ -392,6 +392,54 @@ struct ChannelAgc {
     }
 };
 
+// The state of the channel noise blanker (sddc_ddc_channel_blank_*; blanker_math.h): the parameters
+// [nch][2] = (thr, qmin) (empty = off) with their device copy, the guard, the reference and the format,
+// the stream position (host) and each channel's state (block powers, unfinished block, last g samples,
+// last hit) as [nch][kBlankStateWords] words in two device buffers that swap per launch, as ChannelAgc's
+// do.  A CPU handle keeps the state in state_h.  d_in / d_out / d_count are the host call's device
+// buffers.  All under the handle's mu.
+struct ChannelBlanker {
+    std::vector<float> par;
+    int nch = 0, guard = 0, ref_blocks = 0, ref_mode = 0, fmt = 0;
+    uint64_t pos = 0;
+    float *d_par = nullptr;
+    uint32_t *d_state[2] = {};
+    int cur = 0;
+    std::vector<sddc::cpu::R2iq::BlankerChannel> state_h;
+    Readers readers;
+    int max_wgs = 0, run_blocks = 0;   // SDDC_DDC_PARAM_CHNB_MAX_WGS, _RUN_BLOCKS (0: chosen from the size)
+    void *d_in = nullptr, *d_out = nullptr;
+    uint32_t *d_count = nullptr;
+    size_t in_cap = 0, out_cap = 0, count_cap = 0;   // bytes, bytes, counters
+
+    size_t state_words() const { return (size_t)nch * sddc::kBlankStateWords; }
+    void clear()
+    {
+        par.clear();
+        nch = guard = ref_blocks = ref_mode = fmt = 0;
+        pos = 0;
+        state_h.clear();
+        if (d_par) (void)hipFree(d_par);
+        d_par = nullptr;
+        for (uint32_t *&p : d_state) {
+            if (p) (void)hipFree(p);
+            p = nullptr;
+        }
+        cur = 0;
+    }
+    void free_all()
+    {
+        clear();
+        if (d_in) (void)hipFree(d_in);
+        if (d_out) (void)hipFree(d_out);
+        if (d_count) (void)hipFree(d_count);
+        d_in = d_out = nullptr;
+        d_count = nullptr;
+        in_cap = out_cap = count_cap = 0;
+        readers.clear();
+    }
+};
+
 }  // namespace
 
 struct sddc_ddc {
@@ -563,6 +611,7 @@ struct sddc_ddc {
     ChannelDemod chdem;                    // max_wgs: SDDC_DDC_PARAM_CHDEM_MAX_WGS
     ChannelAudio chaud;
     ChannelAgc chagc;
+    ChannelBlanker chnb;
 
     // CPU handle (device SDDC_DDC_DEVICE_CPU): the AVX2 backend; no HIP object above exists
     std::unique_ptr<sddc::cpu::R2iq> cpu;
@@ -917,6 +966,7 @@ int sddc_ddc_destroy(sddc_ddc_t *h)
         (void)h->chdem.readers.sync();
         (void)h->chaud.readers.sync();
         (void)h->chagc.readers.sync();
+        (void)h->chnb.readers.sync();
         if (h->d_tables) (void)hipFree(h->d_tables);
         for (auto &sl : h->hs) {
             if (sl.d_in) (void)hipFree(sl.d_in);
@@ -953,6 +1003,7 @@ int sddc_ddc_destroy(sddc_ddc_t *h)
         h->chdem.free_all();
         h->chaud.free_all();
         h->chagc.free_all();
+        h->chnb.free_all();
         if (h->fsa.h_ring) (void)hipHostFree(h->fsa.h_ring);   // its writers were waited for above
         h->readers.clear();
         h->ch_readers.clear();
@@ -1499,6 +1550,15 @@ int sddc_ddc_internal_set_param(sddc_ddc_t *h, int param, int value)
         if (value < 0 || value > (1 << 20))
             return fail(SDDC_ERR_ARG, "channel AGC run length %d outside 0..2^20 blocks", value);
         h->chagc.run_blocks = value;
+        return SDDC_OK;
+    case SDDC_DDC_PARAM_CHNB_MAX_WGS:
+        if (value < 0) return fail(SDDC_ERR_ARG, "channel blanker workgroup cap %d is negative", value);
+        h->chnb.max_wgs = value;
+        return SDDC_OK;
+    case SDDC_DDC_PARAM_CHNB_RUN_BLOCKS:
+        if (value < 0 || value > (1 << 20))
+            return fail(SDDC_ERR_ARG, "channel blanker run length %d outside 0..2^20 blocks", value);
+        h->chnb.run_blocks = value;
         return SDDC_OK;
     default:
         return fail(SDDC_ERR_ARG, "unknown parameter %d", param);
@@ -3022,6 +3082,228 @@ int sddc_ddc_channel_agc_host(sddc_ddc_t *h, const void *in, int nch, size_t nsa
             HIP_TRY(hipMemcpy2DAsync(out, out_stride * os, st.d_out, out_stride * os, nsamp * os, (size_t)nch,
                                      hipMemcpyDeviceToHost, h->stream));
         if (env) HIP_TRY(hipMemcpyAsync(env, st.d_env, (size_t)nch * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(h->stream));   // also after a failed launch: the caller's input is free again
+    return rc;
+}
+
+/* ---- channel noise blanker: a streaming per-channel impulse blanker on IQ -------------------- */
+static_assert(SDDC_DDC_BLANKER_BLOCK == sddc::blank::kBlankBlock && SDDC_DDC_BLANKER_MAX_GUARD == sddc::blank::kBlankMaxGuard &&
+                  SDDC_DDC_BLANKER_MAX_REF_BLOCKS == sddc::blank::kBlankMaxRef && SDDC_DDC_BLANKER_MEAN == sddc::blank::kBlankMean &&
+                  SDDC_DDC_BLANKER_MEDIAN == sddc::blank::kBlankMedian,
+              "the arithmetic header's constants are the ABI's");
+
+int sddc_ddc_blanker_threshold(double db, float *k2)
+{
+    if (!k2) return fail(SDDC_ERR_ARG, "blanker_threshold: null k2");
+    if (!std::isfinite(db) || db < 0.0 || db > 120.0)
+        return fail(SDDC_ERR_ARG, "blanker_threshold: %g dB is outside 0..120", db);
+    *k2 = (float)std::pow(10.0, db / 10.0);
+    return SDDC_OK;
+}
+
+int sddc_ddc_set_channel_blanker(sddc_ddc_t *h, const float *params, int nch, int guard, int ref_blocks, int ref_mode,
+                                 int format)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    const bool off = !params || nch == 0;
+    std::vector<float> par;
+    if (!off) {
+        if (nch < 1 || nch > SDDC_DDC_MAX_CHANNELS)
+            return fail(SDDC_ERR_ARG, "channel blanker: nch %d outside 1..%d", nch, SDDC_DDC_MAX_CHANNELS);
+        if (guard < 0 || guard > SDDC_DDC_BLANKER_MAX_GUARD)
+            return fail(SDDC_ERR_ARG, "channel blanker: guard %d outside 0..%d", guard, SDDC_DDC_BLANKER_MAX_GUARD);
+        if (ref_blocks < 1 || ref_blocks > SDDC_DDC_BLANKER_MAX_REF_BLOCKS)
+            return fail(SDDC_ERR_ARG, "channel blanker: ref_blocks %d outside 1..%d", ref_blocks, SDDC_DDC_BLANKER_MAX_REF_BLOCKS);
+        if (ref_mode != SDDC_DDC_BLANKER_MEAN && ref_mode != SDDC_DDC_BLANKER_MEDIAN)
+            return fail(SDDC_ERR_ARG, "channel blanker: unknown reference mode %d", ref_mode);
+        if (format != SDDC_DDC_FMT_CF32 && format != SDDC_DDC_FMT_CS16)
+            return fail(SDDC_ERR_ARG, "channel blanker: unknown sample format %d", format);
+        const float k2max = 1099511627776.f, qmax = 1208925819614629174706176.f;   // 2^40, 2^80
+        for (int c = 0; c < nch; c++) {
+            const float k2 = params[2 * c], qmin = params[2 * c + 1];
+            if (!std::isfinite(k2) || !std::isfinite(qmin))
+                return fail(SDDC_ERR_ARG, "channel blanker: a parameter of channel %d is not finite", c);
+            if (!(k2 == 0.f || (k2 >= 1.f && k2 <= k2max)))
+                return fail(SDDC_ERR_ARG, "channel blanker: the threshold %g of channel %d is neither 0 nor in [1, 2^40]", (double)k2, c);
+            if (!(qmin >= 0.f && qmin <= qmax))
+                return fail(SDDC_ERR_ARG, "channel blanker: the floor %g of channel %d is outside [0, 2^80]", (double)qmin, c);
+        }
+        try {
+            par.resize((size_t)nch * 2);
+        } catch (const std::exception &ex) {
+            return fail(SDDC_ERR_NOMEM, "channel blanker: %s", ex.what());
+        }
+        for (int c = 0; c < nch; c++) {
+            par[2 * c] = sddc::blank::blank_thr(params[2 * c]);
+            par[2 * c + 1] = params[2 * c + 1] == 0.f ? 0.f : params[2 * c + 1];   // -0 as +0
+        }
+    }
+    std::lock_guard<std::mutex> lk(h->mu);
+    ChannelBlanker &st = h->chnb;
+    if (h->cpu) {
+        st.clear();
+        if (off) return SDDC_OK;
+        try {
+            st.state_h.assign((size_t)nch, sddc::cpu::R2iq::BlankerChannel());
+        } catch (const std::exception &ex) {
+            st.clear();
+            return fail(SDDC_ERR_NOMEM, "channel blanker: %s", ex.what());
+        }
+    } else {
+        DeviceGuard g(h->device);
+        HIP_TRY(g.err);
+        HIP_TRY(st.readers.sync());   // earlier launches, on any stream, may still use the state
+        st.clear();                   // a failed upload leaves the stage off
+        if (off) return SDDC_OK;
+        const size_t nstate = (size_t)nch * sddc::kBlankStateWords;
+        hipError_t e = hipMalloc(&st.d_par, par.size() * sizeof(float));
+        for (uint32_t *&p : st.d_state)
+            if (e == hipSuccess) e = hipMalloc(&p, nstate * sizeof(uint32_t));
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            st.clear();
+            return fail(SDDC_ERR_NOMEM, "channel blanker: no device memory for %d channels", nch);
+        }
+        e = hipMemcpy(st.d_par, par.data(), par.size() * sizeof(float), hipMemcpyHostToDevice);
+        // zeroed on the handle's stream and waited for: the first launch may be on any stream
+        for (uint32_t *p : st.d_state)
+            if (e == hipSuccess) e = hipMemsetAsync(p, 0, nstate * sizeof(uint32_t), h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) {
+            st.clear();
+            HIP_TRY(e);
+        }
+    }
+    st.par = std::move(par);
+    st.nch = nch;
+    st.guard = guard;
+    st.ref_blocks = ref_blocks;
+    st.ref_mode = ref_mode;
+    st.fmt = format;
+    st.pos = 0;
+    return SDDC_OK;
+}
+
+int sddc_ddc_channel_blanker_reset(sddc_ddc_t *h)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    ChannelBlanker &st = h->chnb;
+    if (st.par.empty()) return fail(SDDC_ERR_STATE, "channel blanker reset: no blanker set");
+    if (h->cpu) {
+        std::fill(st.state_h.begin(), st.state_h.end(), sddc::cpu::R2iq::BlankerChannel());
+    } else {
+        DeviceGuard g(h->device);
+        HIP_TRY(g.err);
+        HIP_TRY(st.readers.sync());   // earlier launches, on any stream, may still use the state
+        HIP_TRY(hipMemsetAsync(st.d_state[st.cur], 0, st.state_words() * sizeof(uint32_t), h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));   // the next launch may be on any stream
+    }
+    st.pos = 0;
+    return SDDC_OK;
+}
+
+// the checks both calls share (under h->mu)
+static int check_chnb_args(const sddc_ddc_t *h, const void *iq, int nch, size_t nsamp, size_t in_stride, const void *out,
+                           size_t out_stride, const uint32_t *count)
+{
+    const ChannelBlanker &st = h->chnb;
+    if (st.par.empty()) return fail(SDDC_ERR_STATE, "channel blanker: no blanker set");
+    if (nch != st.nch)
+        return fail(SDDC_ERR_STATE, "channel blanker: the blanker is set for %d channels, the call has %d", st.nch, nch);
+    if (nsamp == 0 || nsamp > ((size_t)1 << 40)) return fail(SDDC_ERR_ARG, "nsamp must be in 1..2^40 (got %zu)", nsamp);
+    if (nch > 1 && (in_stride < 2 * nsamp || (in_stride & 1) != 0))
+        return fail(SDDC_ERR_ARG, "in_stride must be even and >= 2 nsamp (got %zu, nsamp %zu)", in_stride, nsamp);
+    if (nch > 1 && (out_stride < 2 * nsamp || (out_stride & 1) != 0))
+        return fail(SDDC_ERR_ARG, "out_stride must be even and >= 2 nsamp (got %zu, nsamp %zu)", out_stride, nsamp);
+    if (!iq || !out) return fail(SDDC_ERR_ARG, "null buffer");
+    const uintptr_t comp = st.fmt == SDDC_DDC_FMT_CS16 ? 2 : 4, sample = 2 * comp;
+    if (((uintptr_t)iq & (sample - 1)) != 0) return fail(SDDC_ERR_ARG, "iq must be %d-byte aligned", (int)sample);
+    if (((uintptr_t)out & (sample - 1)) != 0) return fail(SDDC_ERR_ARG, "the output must be %d-byte aligned", (int)sample);
+    if (((uintptr_t)count & 3) != 0) return fail(SDDC_ERR_ARG, "the counts must be 4-byte aligned");
+    // the spans from the first channel's first sample to the last channel's last one
+    const uintptr_t ia = (uintptr_t)iq, oa = (uintptr_t)out;
+    const uintptr_t ib = ia + ((uintptr_t)(nch - 1) * (nch > 1 ? in_stride : 0) + 2 * nsamp) * comp;
+    const uintptr_t ob = oa + ((uintptr_t)(nch - 1) * (nch > 1 ? out_stride : 0) + 2 * nsamp) * comp;
+    if (ia < ob && oa < ib) return fail(SDDC_ERR_ARG, "the input and the output overlap");
+    return SDDC_OK;
+}
+
+// The call in launches of at most kBlankMaxLaunch samples per channel (the kernels index a launch with
+// an int), two kernels each on s.  d_count, if given, is zeroed first and every launch adds to it.
+static int chnb_launch(sddc_ddc_t *h, const void *d_iq, int nch, size_t nsamp, size_t in_stride, void *d_out,
+                       size_t out_stride, uint32_t *d_count, hipStream_t s)
+{
+    ChannelBlanker &st = h->chnb;
+    HIP_TRY(st.readers.order_before(s));
+    const bool cs16 = st.fmt == SDDC_DDC_FMT_CS16;
+    const size_t sample = cs16 ? 4 : 8;
+    hipError_t e = hipSuccess;
+    if (d_count) e = hipMemsetAsync(d_count, 0, (size_t)nch * sizeof(uint32_t), s);
+    for (size_t done = 0; done < nsamp && e == hipSuccess;) {
+        size_t n = nsamp - done;
+        if (n > sddc::kBlankMaxLaunch) n = sddc::kBlankMaxLaunch;
+        e = sddc::launch_channel_blank(h->tables, static_cast<const char *>(d_iq) + done * sample, cs16, nch, n, in_stride,
+                                       st.pos, st.d_par, st.guard, st.ref_blocks, st.ref_mode, st.d_state[st.cur],
+                                       st.d_state[st.cur ^ 1], static_cast<char *>(d_out) + done * sample, out_stride,
+                                       d_count, st.max_wgs, st.run_blocks, h->device, s);
+        if (e != hipSuccess) break;
+        st.cur ^= 1;
+        st.pos += n;
+        done += n;
+    }
+    const hipError_t er = st.readers.record(s);   // whatever was enqueued stays ordered
+    HIP_TRY(e);
+    HIP_TRY(er);
+    return SDDC_OK;
+}
+
+int sddc_ddc_channel_blank_device(sddc_ddc_t *h, const void *d_iq, int nch, size_t nsamp, size_t in_stride, void *d_out,
+                                  size_t out_stride, uint32_t *d_count, void *hip_stream)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->cpu) return fail(SDDC_ERR_STATE, "channel_blank_device: a CPU handle has no device path");
+    if (int rc = check_chnb_args(h, d_iq, nch, nsamp, in_stride, d_out, out_stride, d_count)) return rc;
+    DeviceGuard g(h->device);
+    HIP_TRY(g.err);
+    return chnb_launch(h, d_iq, nch, nsamp, in_stride, d_out, out_stride, d_count, (hipStream_t)hip_stream);
+}
+
+int sddc_ddc_channel_blank_host(sddc_ddc_t *h, const void *iq, int nch, size_t nsamp, size_t in_stride, void *out,
+                                size_t out_stride, uint32_t *count)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (int rc = check_chnb_args(h, iq, nch, nsamp, in_stride, out, out_stride, count)) return rc;
+    ChannelBlanker &st = h->chnb;
+    const bool cs16 = st.fmt == SDDC_DDC_FMT_CS16;
+    if (h->cpu) {
+        sddc::cpu::R2iq::channel_blank(iq, cs16, nch, nsamp, nch > 1 ? in_stride : 0, st.par.data(), st.guard, st.ref_blocks,
+                                       st.ref_mode, st.pos, st.state_h.data(), out, nch > 1 ? out_stride : 0, count);
+        st.pos += nsamp;
+        return SDDC_OK;
+    }
+    DeviceGuard g(h->device);
+    HIP_TRY(g.err);
+    // the spans that hold every channel's samples and outputs
+    const size_t comp = cs16 ? 2 : 4;
+    const size_t in_bytes = ((size_t)(nch - 1) * (nch > 1 ? in_stride : 0) + 2 * nsamp) * comp;
+    const size_t out_bytes = ((size_t)(nch - 1) * (nch > 1 ? out_stride : 0) + 2 * nsamp) * comp;
+    if (int rc = grow_device_buffer(&st.d_in, &st.in_cap, in_bytes, "channel_blank_host", "input bytes")) return rc;
+    if (int rc = grow_device_buffer(&st.d_out, &st.out_cap, out_bytes, "channel_blank_host", "output bytes")) return rc;
+    if (count)
+        if (int rc = grow_device_buffer(&st.d_count, &st.count_cap, (size_t)nch, "channel_blank_host", "counters")) return rc;
+    HIP_TRY(hipMemcpyAsync(st.d_in, iq, in_bytes, hipMemcpyHostToDevice, h->stream));
+    const int rc = chnb_launch(h, st.d_in, nch, nsamp, in_stride, st.d_out, out_stride, count ? st.d_count : nullptr, h->stream);
+    if (rc == SDDC_OK) {   // the streams alone: the caller's memory between them stays as it is
+        if (nch == 1 || out_stride == 2 * nsamp)
+            HIP_TRY(hipMemcpyAsync(out, st.d_out, out_bytes, hipMemcpyDeviceToHost, h->stream));
+        else
+            HIP_TRY(hipMemcpy2DAsync(out, out_stride * comp, st.d_out, out_stride * comp, 2 * nsamp * comp, (size_t)nch,
+                                     hipMemcpyDeviceToHost, h->stream));
+        if (count) HIP_TRY(hipMemcpyAsync(count, st.d_count, (size_t)nch * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
     }
     HIP_TRY(hipStreamSynchronize(h->stream));   // also after a failed launch: the caller's input is free again
     return rc;

@@ -95,6 +95,16 @@ extern "C" {
  * entry points do (A/B of the gap between consecutive dispatches). */
 #define SDDC_DDC_PARAM_LAZY_RECORD 20
 
+/* SDDC_DDC_PARAM_CHNB_MAX_WGS = n > 0: each of the channel blanker's two grids is at most n workgroups,
+ * as param 18 for the AGC; 0 (default): one workgroup per run (or per channel), or full residency with
+ * a loop.  The grid changes no output bit and no count (tests). */
+#define SDDC_DDC_PARAM_CHNB_MAX_WGS 21
+
+/* SDDC_DDC_PARAM_CHNB_RUN_BLOCKS = n in 1..2^20: a wave of the channel blanker owns n consecutive blocks
+ * of a channel (and recomputes what it needs of the blocks before them); 0: chosen from the call's
+ * size, 32..128.  The run length changes no output bit and no count (tests). */
+#define SDDC_DDC_PARAM_CHNB_RUN_BLOCKS 22
+
 int sddc_ddc_internal_set_param(sddc_ddc_t *h, int param, int value);
 /* A given table of n relative shares (n = the d = 0 kernel's full-residency grid, 4 x CUs) used as
  * it is, without clamps or measurements, until n = 0 clears it (tests). */

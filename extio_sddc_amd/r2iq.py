@@ -168,6 +168,18 @@ def agc_decay(tau_samples: float) -> float:
     return float(d.value)
 
 
+BLANKER_BLOCK = 256                       # SDDC_DDC_BLANKER_BLOCK: the noise blanker's block length B
+BLANKER_MEAN, BLANKER_MEDIAN = 0, 1       # SDDC_DDC_BLANKER_*: the reference of the last M block powers
+
+
+def blanker_threshold(db: float) -> float:
+    """The noise blanker's threshold k2 of db decibels above the reference power: float32(10^(db / 10)),
+    0..120 dB (sddc_ddc_blanker_threshold)."""
+    k2 = ctypes.c_float()
+    check(_lib.load().sddc_ddc_blanker_threshold(float(db), ctypes.addressof(k2)))
+    return float(k2.value)
+
+
 def psd_to_dbfs(psd) -> np.ndarray:
     """R2iq.spectrum's output in dB relative to a full-scale real tone (amplitude 32768 reads
     32768^2 / 4 at its bin centre): 10 log10(4 psd / 32768^2); -inf where psd is 0."""
@@ -199,6 +211,7 @@ class R2iq:
         self._demod = None   # (nch, out_format) of setChannelDemodulator
         self._audio = None   # (nch, in_format, out_format) of setChannelAudioFilter
         self._agc = None     # (nch, in_format, out_format) of setChannelAgc
+        self._blanker = None  # (nch, format) of setChannelBlanker
 
     # -- lifecycle --------------------------------------------------------
     @property
@@ -801,6 +814,89 @@ class R2iq:
         check(self._L.sddc_ddc_channel_agc_device(self._h, d_in.data_ptr(), nch, nsamp, in_stride, d_out.data_ptr(),
                                                   out_stride, None if d_env is None else d_env.data_ptr(),
                                                   _stream_handle(stream)))
+
+    # -- channel noise blanker --------------------------------------------------------
+    def setChannelBlanker(self, params, guard: int, ref_blocks: int, ref_mode: int = BLANKER_MEAN,
+                          fmt: int = FMT_CF32) -> None:
+        """The streaming impulse blanker of channel_blank: params is float32 [nch, 2], per channel (k2,
+        qmin): the threshold as a power ratio over the reference (blanker_threshold; 0: the channel is
+        bypassed, a pure delay) and an absolute floor on |x|^2 below which nothing is blanked.  guard:
+        samples blanked on each side of a hit, 0..64, and the delay of every channel; ref_blocks: the
+        reference is the BLANKER_MEAN or BLANKER_MEDIAN power of the last 1..16 blocks of 256 samples;
+        fmt: FMT_CF32 or FMT_CS16, the format of this stage's buffers.  Every call zeroes the state and
+        the stream position.  params=None turns the stage off."""
+        if params is None or np.size(params) == 0:
+            check(self._L.sddc_ddc_set_channel_blanker(self._h, None, 0, 0, 0, 0, 0))
+            self._blanker = None
+            return
+        p = np.ascontiguousarray(np.asarray(params, np.float32))
+        if p.ndim != 2 or p.shape[1] != 2:
+            raise DDCError(-1, "params must be [nch, 2]")
+        check(self._L.sddc_ddc_set_channel_blanker(self._h, p.ctypes.data, p.shape[0], int(guard), int(ref_blocks),
+                                                   int(ref_mode), int(fmt)))
+        self._blanker = (p.shape[0], int(fmt))
+
+    def resetChannelBlanker(self) -> None:
+        """Zero every channel's state and the stream position: the next call starts a new stream."""
+        check(self._L.sddc_ddc_channel_blanker_reset(self._h))
+
+    def channel_blank(self, x: np.ndarray, count: bool = False):
+        """The blanker on a host array: x is complex64 [nch, nsamp] (FMT_CS16: int16 [nch, nsamp, 2]), any
+        nsamp >= 1; a single stream may drop the channel axis.  Returns the same shape and type, delayed
+        by the guard, with count=True also the uint32 [nch] blanked outputs of this call, and keeps every
+        channel's state for the next call."""
+        if self._blanker is None:
+            raise DDCError(-4, "no channel blanker set")
+        nch, fmt = self._blanker
+        if fmt == FMT_CS16:
+            x = np.asarray(x, np.int16)
+            if x.ndim == 2:
+                x = x[None]
+            if x.ndim != 3 or x.shape[2] != 2 or x.shape[1] < 1:
+                raise DDCError(-1, "x must be int16 [nch, nsamp, 2] with nsamp >= 1")
+        else:
+            x = np.asarray(x, np.complex64)
+            if x.ndim == 1:
+                x = x[None]
+            if x.ndim != 2 or x.shape[1] < 1:
+                raise DDCError(-1, "x must be complex64 [nch, nsamp] with nsamp >= 1")
+        x = np.ascontiguousarray(x)
+        nsamp = x.shape[1]
+        out = np.empty_like(x)
+        cnt = np.empty(x.shape[0], np.uint32) if count else None
+        check(self._L.sddc_ddc_channel_blank_host(self._h, x.ctypes.data, x.shape[0], nsamp, 2 * nsamp, out.ctypes.data,
+                                                  2 * nsamp, None if cnt is None else cnt.ctypes.data))
+        return (out, cnt) if count else out
+
+    def channel_blank_device(self, d_iq, nch: int, nsamp: int, in_stride: int, d_out, out_stride: int, d_count=None,
+                             stream=None) -> None:
+        """The blanker on a device buffer laid out as process_channels_device writes it: d_iq is a float32
+        (FMT_CS16: int16) device tensor of components, channel c's nsamp IQ samples at c * in_stride
+        components; d_out the same type, channel c's nsamp outputs at c * out_stride; strides even and
+        >= 2 * nsamp; the two must not overlap; d_count None or an int32 device tensor of nch values that
+        receives the blanked outputs of this call.  Enqueued on `stream` like process_device; the calls
+        of one handle run in call order."""
+        import torch
+        if self._blanker is None:
+            raise DDCError(-4, "no channel blanker set")
+        if nch < 1 or nsamp < 1:
+            raise DDCError(-1, "nch and nsamp must be >= 1")
+        if not (d_iq.is_cuda and d_out.is_cuda and (d_count is None or d_count.is_cuda)):
+            raise DDCError(-1, "device path needs device tensors")
+        want = torch.int16 if self._blanker[1] == FMT_CS16 else torch.float32
+        if d_iq.dtype != want or d_out.dtype != want:
+            raise DDCError(-1, f"d_iq and d_out must be {want}")
+        if not (d_iq.is_contiguous() and d_out.is_contiguous()):
+            raise DDCError(-1, "tensors must be contiguous")
+        for name, t, stride in (("d_iq", d_iq, in_stride), ("d_out", d_out, out_stride)):
+            need = (nch - 1) * stride + 2 * nsamp
+            if t.numel() < need:
+                raise DDCError(-1, f"{name} has {t.numel()} components, need {need}")
+        if d_count is not None and (d_count.dtype != torch.int32 or not d_count.is_contiguous() or d_count.numel() < nch):
+            raise DDCError(-1, f"d_count must be a contiguous int32 tensor of at least {nch} values")
+        check(self._L.sddc_ddc_channel_blank_device(self._h, d_iq.data_ptr(), nch, nsamp, in_stride, d_out.data_ptr(),
+                                                    out_stride, None if d_count is None else d_count.data_ptr(),
+                                                    _stream_handle(stream)))
 
 
 def _check_device_buffers(d_in, nblk, d_out, out_floats, fmt=0):

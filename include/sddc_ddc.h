@@ -347,8 +347,8 @@ size_t sddc_ddc_channel_decimate_samples(int factor, size_t nsamp);
 int sddc_ddc_channel_decimate_device(sddc_ddc_t *h, const void *d_iq, int nch, size_t nsamp, size_t in_stride,
                                      float *d_out, size_t out_stride, void *hip_stream);
 /* Host buffers, the same layouts.  GPU handle: copy in, kernel, copy back, synchronous, in device
- * buffers of its own; it advances the same device tails as the device call.  CPU handle: the AVX2
- * backend, the same definition and bound (another fixed order of the sum). */
+ * buffers of its own; it advances the same device tails as the device call.  CPU handle: the same
+ * definition, bound and order of the sum as the device: bit-identical to a GPU handle. */
 int sddc_ddc_channel_decimate_host(sddc_ddc_t *h, const void *iq, int nch, size_t nsamp, size_t in_stride,
                                    float *out, size_t out_stride);
 
@@ -665,6 +665,84 @@ int sddc_ddc_channel_agc_device(sddc_ddc_t *h, const void *d_in, int nch, size_t
  * loop through the same arithmetic header. */
 int sddc_ddc_channel_agc_host(sddc_ddc_t *h, const void *in, int nch, size_t nsamp, size_t in_stride, void *out,
                               size_t out_stride, float *env);
+
+/* ---- channel noise blanker: a streaming per-channel impulse blanker on IQ -------------------
+ * Every stage after the DDC is linear or memoryless on the IQ, so an impulse (ignition, power-line
+ * arcs, switching supplies) that is a few samples long where the channel is still wide becomes a
+ * filter-long ringing burst after the channel decimator.  The blanker therefore sits between the DDC's
+ * channel output (sddc_ddc_process_channels_device, or a single d = 0..6 stream) and the decimator: it
+ * zeroes the samples whose power exceeds a multiple of the recent mean block power, with a guard of g
+ * samples on each side, and delays every channel by g samples.  It is feed-forward.  What this blanker
+ * is NOT: it zeroes, it does not interpolate or hold.  The reference contains the impulses themselves:
+ * MEAN is raised by them and reacts to a level jump within one block; MEDIAN ignores a minority of
+ * contaminated blocks but takes M / 2 blocks to follow a jump, so a keyed strong carrier is chewed at
+ * each attack.  After blocks of exact zeros the reference is 0, and only qmin keeps the next samples
+ * from being blanked.
+ *
+ * The definition (normative; csrc/blanker_math.h holds the operations, shared by both backends, float,
+ * contraction off, only *, +, comparisons and selects).  B = SDDC_DDC_BLANKER_BLOCK = 256.  Per handle:
+ * the guard g (0..SDDC_DDC_BLANKER_MAX_GUARD), the reference length M (1..
+ * SDDC_DDC_BLANKER_MAX_REF_BLOCKS blocks), the reference mode and the stream format (SDDC_DDC_FMT_CF32 or
+ * _CS16: the format of the buffers given to this stage, not the handle's current output format).  Per
+ * channel c two floats: k2_c, the threshold as a power ratio (0: the channel is bypassed, a pure delay),
+ * and qmin_c, an absolute floor on |x|^2 below which nothing is ever a hit.  i >= 0 is the stream index
+ * since the last set or reset, k = i div B its block, x[i] = (I, Q) as float: CF32 as stored, CS16
+ * (float)v with no scale (qmin is in codes squared).
+ *   Power.      q[i] = (I * I) + (Q * Q), three roundings; q is non-finite if !(q <= FLT_MAX).
+ *   Block power. p_k: the balanced pairwise tree over the 256 values of block k in sample order (level 0
+ *               adds (q[0] + q[1]), (q[2] + q[3]), ...; eight levels); a non-finite q enters as 0.
+ *   Reference.  n = min(k, M); the values p_{k-n} .. p_{k-1} (full blocks only).  MEAN: S = (..((p_{k-n}
+ *               + p_{k-n+1}) + p_{k-n+2}) ..) + p_{k-1}, P_k = S * rn[n], rn[n] = (float)(1.0 / n).
+ *               MEDIAN: P_k is the value of rank (n - 1) div 2 (0-based, ascending) of the n values.
+ *               n = 0 (block 0 of a stream): no finite sample of it is a hit.
+ *   Threshold.  thr_c = (float)((double)k2_c / 256.0) at set time; t = thr_c * P_k; t_k = (t > qmin_c) ?
+ *               t : qmin_c.
+ *   Hit.        k2_c > 0: hit[i] = (q[i] > t_k) or q[i] non-finite.  A bypassed channel has no hits.
+ *   Mask.       blank[i] if any hit[j] with |j - i| <= g, j >= 0.
+ *   Output.     A call of nsamp samples writes nsamp samples per channel; y[n] = 0 for n < g, otherwise
+ *               y[n] = blank[n - g] ? (+0, +0) : x[n - g], a kept sample bit for bit (float payloads,
+ *               int16 codes).
+ *   Count.      Optional: per channel the outputs n >= g of this call with blank[n - g].  The counts of
+ *               the calls of a cut add up to the count of the uncut call.
+ * A written sample depends only on the samples of its own block, the M blocks before it and g samples
+ * after it, so outputs and counts are bit-identical from run to run, for any grid, run length and cut
+ * of a stream into calls, for a channel alone or among others, and between a GPU handle and a CPU
+ * handle.  Range of that guarantee: components that are 0 or of magnitude in [2^-40, 2^40] (then q and
+ * the block powers are 0 or in [2^-80, 2^89], S < 2^93, thr in [2^-8, 2^32], t < 2^125 and, where
+ * P > 0, t >= 2^-88: no overflow, nothing subnormal on the deciding path; blanker_math.h has the
+ * derivation).  Validity, checked at set time: everything finite; k2 == 0 or 1 <= k2 <= 2^40;
+ * 0 <= qmin <= 2^80; the ranges above; anything else returns SDDC_ERR_ARG and sets nothing.
+ * State per handle, on the device for a GPU handle, independent of every other stage's: the position,
+ * the last M block powers, the unfinished block's q values, the last g stored samples and the position
+ * of the last hit among the last 2 g samples (all the mask needs of their hit flags). */
+#define SDDC_DDC_BLANKER_BLOCK 256
+#define SDDC_DDC_BLANKER_MAX_GUARD 64
+#define SDDC_DDC_BLANKER_MAX_REF_BLOCKS 16
+#define SDDC_DDC_BLANKER_MEAN 0
+#define SDDC_DDC_BLANKER_MEDIAN 1
+/* k2 = 10^(db / 10) rounded to float.  SDDC_ERR_ARG outside 0..120 dB, not finite, or k2 NULL.  Stateless. */
+int sddc_ddc_blanker_threshold(double db, float *k2);
+/* params: host array [nch][2] = (k2, qmin); 1 <= nch <= SDDC_DDC_MAX_CHANNELS; a violation returns
+ * SDDC_ERR_ARG and sets nothing.  params NULL or nch == 0 turns the stage off and frees its state.  Every
+ * set call zeroes the state and the position, and waits for the stage's launches in flight. */
+int sddc_ddc_set_channel_blanker(sddc_ddc_t *h, const float *params, int nch, int guard, int ref_blocks, int ref_mode,
+                                 int format);
+/* zero the state and the position: the next call starts a new stream (SDDC_ERR_STATE: no blanker set) */
+int sddc_ddc_channel_blanker_reset(sddc_ddc_t *h);
+/* GPU handles; enqueued on hip_stream, returns after launch.  Layouts as for sddc_ddc_channel_decimate_
+ * device, on both sides and in the set format: channel c's nsamp samples at c * stride components,
+ * strides even and >= 2 nsamp for nch > 1, bases aligned to one complex sample; any 1 <= nsamp <= 2^40;
+ * the input and the output must not overlap; nothing is written between the streams or outside them.
+ * d_count: NULL, or nch device uint32_t.  SDDC_ERR_STATE: no blanker set, another nch than the set one,
+ * a CPU handle.  SDDC_ERR_ARG: the rest.  A failed call changes no state.  The calls of one handle share
+ * the state and the position: they run one after the other in call order, whatever their streams. */
+int sddc_ddc_channel_blank_device(sddc_ddc_t *h, const void *d_iq, int nch, size_t nsamp, size_t in_stride, void *d_out,
+                                  size_t out_stride, uint32_t *d_count, void *hip_stream);
+/* Host buffers, the same layouts; count NULL or nch uint32_t.  GPU handle: copy in, kernels, copy back,
+ * synchronous; it advances the same device state as the device call.  CPU handle: the definition's
+ * loop through the same arithmetic header. */
+int sddc_ddc_channel_blank_host(sddc_ddc_t *h, const void *iq, int nch, size_t nsamp, size_t in_stride, void *out,
+                                size_t out_stride, uint32_t *count);
 
 /* ---- ingest ---------------------------------------
  * Pin a caller-owned host region (hipHostRegister) so the host path DMAs blocks
