@@ -92,6 +92,11 @@ SIGNATURES = {
     "sddc_ddc_channel_blanker_reset": (_I, [_P]),
     "sddc_ddc_channel_blank_device": (_I, [_P, _P, _I, _SZ, _SZ, _P, _SZ, _P, _P]),
     "sddc_ddc_channel_blank_host": (_I, [_P, _P, _I, _SZ, _SZ, _P, _SZ, _P]),
+    "sddc_ddc_squelch_blocks": (_I, [ctypes.c_double, ctypes.c_double, _P]),
+    "sddc_ddc_set_channel_squelch": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I]),
+    "sddc_ddc_channel_squelch_reset": (_I, [_P]),
+    "sddc_ddc_channel_squelch_device": (_I, [_P, _P, _P, _I, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _P, _P]),
+    "sddc_ddc_channel_squelch_host": (_I, [_P, _P, _P, _I, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _P]),
     "sddc_ddc_register_host": (_I, [_P, _P, _SZ]),
     "sddc_ddc_unregister_host": (_I, [_P, _P]),
     # include/sddc_fft.h

@@ -640,5 +640,68 @@ void R2iq::channel_blank(const void *in, bool cs16, int nch, size_t nsamp, size_
     }
 }
 
+// The channel squelch: squelch_math.h's stream, sample by sample.
+void R2iq::channel_squelch(const void *audio, bool in16, const void *sense, int kind, int nch, size_t nsamp, size_t in_stride,
+                           size_t sense_stride, const int *modes, const float *thr, int attack, int hang, int fade,
+                           uint64_t pos, SquelchChannel *state, void *out, bool out16, size_t out_stride, uint32_t *open,
+                           uint32_t *count, float *level)
+{
+    using namespace squelch;
+    const int B = kSquelchBlock;
+    for (int c = 0; c < nch; c++) {
+        const float *xf = static_cast<const float *>(audio) + (size_t)c * in_stride;
+        const int16_t *xs = static_cast<const int16_t *>(audio) + (size_t)c * in_stride;
+        const float *sf = static_cast<const float *>(sense) + (size_t)c * sense_stride;
+        const int16_t *ss = static_cast<const int16_t *>(sense) + (size_t)c * sense_stride;
+        float *yf = static_cast<float *>(out) + (size_t)c * out_stride;
+        int16_t *ys = static_cast<int16_t *>(out) + (size_t)c * out_stride;
+        const int mode = modes[c];
+        const float To = thr[2 * c], Tc = thr[2 * c + 1];
+        const bool gated = mode == kSquelchLevel || mode == kSquelchNoise;
+        SquelchChannel &st = state[c];
+        int b = (int)(pos % (uint64_t)B);
+        uint32_t cnt = 0;
+        for (size_t i = 0; i < nsamp; i++) {
+            const float x = in16 ? (float)xs[i] : xf[i];
+            float q;
+            switch (kind) {
+            case kSenseSelf: q = squelch_q_real(x); break;
+            case kSenseF32: q = squelch_q_real(sf[i]); break;
+            case kSenseS16: q = squelch_q_real((float)ss[i]); break;
+            case kSenseCF32: q = blank::blank_power(sf[2 * i], sf[2 * i + 1]); break;
+            default: q = blank::blank_power((float)ss[2 * i], (float)ss[2 * i + 1]); break;
+            }
+            const bool fin = blank::blank_finite(q);
+            st.q[b] = fin ? q : 0.f;
+            st.bad |= fin ? 0u : 1u;
+            const uint32_t g = mode == kSquelchOff ? 1u : (gated ? st.open : 0u);
+            const int k = squelch_kind(mode, g, st.gprev, fade);
+            if (out16) {
+                ys[i] = demod::demod_s16(squelch_apply(k, b, x));
+            } else if (k == kPass && !in16) {
+                __builtin_memcpy(&yf[i], &xf[i], 4);   // the stored word: a NaN keeps its payload
+            } else {
+                yf[i] = squelch_apply(k, b, x);
+            }
+            cnt += g;
+            if (++b == B) {
+                const float p = blank::blank_tree(st.q);
+                if (gated) {
+                    bool u, v;
+                    squelch_flags(p, st.bad != 0, mode, To, Tc, &u, &v);
+                    st.gprev = st.open;
+                    squelch_step(u, v, (uint32_t)attack, (uint32_t)hang, &st.r, &st.n, &st.open);
+                }
+                st.level = p;
+                st.bad = 0;
+                b = 0;
+            }
+        }
+        if (open) open[c] = mode == kSquelchOff ? 1u : (gated ? st.open : 0u);
+        if (count) count[c] = cnt;
+        if (level) level[c] = st.level;
+    }
+}
+
 }  // namespace cpu
 }  // namespace sddc

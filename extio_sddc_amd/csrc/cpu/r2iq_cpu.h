@@ -27,6 +27,7 @@
 #include "../audio_iir_math.h"
 #include "../blanker_math.h"
 #include "../demod_math.h"
+#include "../squelch_math.h"
 #include "fft_avx2.hpp"
 
 namespace sddc {
@@ -125,6 +126,23 @@ public:
     static void channel_blank(const void *in, bool cs16, int nch, size_t nsamp, size_t in_stride, const float *par,
                               int guard, int ref_blocks, int ref_mode, uint64_t pos, BlankerChannel *state, void *out,
                               size_t out_stride, uint32_t *count);
+    // The channel squelch (sddc_ddc.h, sddc_ddc_channel_squelch_host; squelch_math.h): the definition's loop,
+    // sample by sample.  Channel c's nsamp audio samples (float, or int16 when in16) at audio + c * in_stride,
+    // its sense samples at sense + c * sense_stride components (kind: squelch::kSense*; kSenseSelf: the
+    // audio), its outputs (float, or int16 when out16) at out + c * out_stride.  modes: [nch]; thr: [nch][2]
+    // = (256 To, 256 Tc); pos: the stream index of the call's first sample; state: [nch], before the call and
+    // replaced by the one after it; open, count, level: null, or [nch].
+    struct SquelchChannel {
+        uint32_t r = 0, n = 0, open = 0;   // the state machine after the last completed block
+        uint32_t gprev = 0;                // the gate of the block before the unfinished one
+        uint32_t bad = 0;                  // the unfinished block holds a non-finite q
+        float level = 0.f;                 // p of the last completed block
+        float q[squelch::kSquelchBlock] = {};   // the unfinished block's q values, non-finite ones as 0
+    };
+    static void channel_squelch(const void *audio, bool in16, const void *sense, int kind, int nch, size_t nsamp,
+                                size_t in_stride, size_t sense_stride, const int *modes, const float *thr, int attack,
+                                int hang, int fade, uint64_t pos, SquelchChannel *state, void *out, bool out16,
+                                size_t out_stride, uint32_t *open, uint32_t *count, float *level);
     // demod_math.h's routines on arrays (the accuracy sweeps of tests/test_channel_demod_cpu.py)
     static void demod_angle_n(const float *im, const float *re, size_t n, float *out);
     static void demod_sincos_n(const uint32_t *words, size_t n, float *c, float *s);

@@ -313,6 +313,24 @@ hipError_t launch_channel_blank(const KernelTables &t, const void *d_iq, int cs1
                                 const uint32_t *d_state_in, uint32_t *d_state_out, void *d_out, size_t out_stride,
                                 uint32_t *d_count, int max_wgs, int run_blocks, int device, hipStream_t s);
 
+// Channel squelch (ddc_channel_squelch.hip, sddc_ddc_channel_squelch_device): one launch set of the block-form
+// gate (squelch_math.h) over nch real audio streams (F32 or S16 in and out, strides in samples) and their
+// sense streams (sense_kind: squelch::kSense*; strides in components, even for the complex kinds; kSenseSelf:
+// the audio, d_sense unused).  pos: the stream index of the first sample; nsamp at most kSquelchMaxLaunch.
+// d_modes: [nch] ints; d_thr: [nch][2] floats (256 To, 256 Tc); d_state_in / d_state_out: [nch][
+// kSquelchStateWords] words before / after (two buffers); d_words: [nch][blocks that hold a sample] words of
+// scratch; d_open, d_count, d_level: null or [nch]; accumulate: d_count holds earlier launches of the same
+// call and is added to.  Three launches on s; max_wgs > 0 caps their grids (tests).  The caller has checked
+// the strides and the alignment of the bases to a sample.
+constexpr int kSquelchStateWords = 264;
+constexpr size_t kSquelchMaxLaunch = (size_t)1 << 28;
+hipError_t launch_channel_squelch(const KernelTables &t, const void *d_audio, int in_s16, const void *d_sense, int sense_kind,
+                                  int nch, size_t nsamp, size_t in_stride, size_t sense_stride, uint64_t pos,
+                                  const int *d_modes, const float *d_thr, int attack, int hang, int fade,
+                                  const uint32_t *d_state_in, uint32_t *d_state_out, uint32_t *d_words, void *d_out,
+                                  int out_s16, size_t out_stride, uint32_t *d_open, uint32_t *d_count, float *d_level,
+                                  int accumulate, int max_wgs, int device, hipStream_t s);
+
 // batched FFTs (fft_batch.hip, include/sddc_fft.h); fft_prepare fills the device's twiddle
 // table once (synchronises s the first time)
 hipError_t fft_prepare(hipStream_t s);

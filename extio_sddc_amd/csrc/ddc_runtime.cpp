@@ -440,6 +440,65 @@ struct ChannelBlanker {
     }
 };
 
+// The state of the channel squelch (sddc_ddc_channel_squelch_*; squelch_math.h): the modes [nch] and the
+// thresholds [nch][2] = (256 To, 256 Tc) (empty = off) with their device copies, the handle's attack, hang,
+// fade, sense kind and formats, the stream position (host) and each channel's state (the state machine, the
+// last level, the unfinished block) as [nch][kSquelchStateWords] words in two device buffers that swap per
+// launch set, as ChannelBlanker's do; d_words is the scratch of one word per channel and block of a launch
+// set, grown on demand.  A CPU handle keeps the state in state_h.  d_in / d_sense / d_out / d_side are the
+// host call's device buffers.  All under the handle's mu.
+struct ChannelSquelch {
+    static constexpr int kDefaultRunBlocks = 4096;
+    std::vector<int> modes;
+    std::vector<float> thr;
+    int nch = 0, attack = 0, hang = 0, fade = 0, sense = 0, in_fmt = 0, out_fmt = 0;
+    uint64_t pos = 0;
+    int *d_modes = nullptr;
+    float *d_thr = nullptr;
+    uint32_t *d_state[2] = {};
+    int cur = 0;
+    uint32_t *d_words = nullptr;
+    size_t words_cap = 0;
+    std::vector<sddc::cpu::R2iq::SquelchChannel> state_h;
+    Readers readers;
+    int max_wgs = 0, run_blocks = 0;   // SDDC_DDC_PARAM_CHSQ_MAX_WGS, _RUN_BLOCKS (0: kDefaultRunBlocks)
+    void *d_in = nullptr, *d_sense = nullptr, *d_out = nullptr;
+    uint32_t *d_side = nullptr;        // [3][nch]: open, count, level
+    size_t in_cap = 0, sense_cap = 0, out_cap = 0, side_cap = 0;   // bytes, bytes, bytes, words
+
+    size_t state_words() const { return (size_t)nch * sddc::kSquelchStateWords; }
+    void clear()
+    {
+        modes.clear();
+        thr.clear();
+        nch = attack = hang = fade = sense = in_fmt = out_fmt = 0;
+        pos = 0;
+        state_h.clear();
+        if (d_modes) (void)hipFree(d_modes);
+        if (d_thr) (void)hipFree(d_thr);
+        d_modes = nullptr;
+        d_thr = nullptr;
+        for (uint32_t *&p : d_state) {
+            if (p) (void)hipFree(p);
+            p = nullptr;
+        }
+        cur = 0;
+    }
+    void free_all()
+    {
+        clear();
+        if (d_words) (void)hipFree(d_words);
+        if (d_in) (void)hipFree(d_in);
+        if (d_sense) (void)hipFree(d_sense);
+        if (d_out) (void)hipFree(d_out);
+        if (d_side) (void)hipFree(d_side);
+        d_words = d_side = nullptr;
+        d_in = d_sense = d_out = nullptr;
+        words_cap = in_cap = sense_cap = out_cap = side_cap = 0;
+        readers.clear();
+    }
+};
+
 }  // namespace
 
 struct sddc_ddc {
@@ -612,6 +671,7 @@ struct sddc_ddc {
     ChannelAudio chaud;
     ChannelAgc chagc;
     ChannelBlanker chnb;
+    ChannelSquelch chsq;
 
     // CPU handle (device SDDC_DDC_DEVICE_CPU): the AVX2 backend; no HIP object above exists
     std::unique_ptr<sddc::cpu::R2iq> cpu;
@@ -967,6 +1027,7 @@ int sddc_ddc_destroy(sddc_ddc_t *h)
         (void)h->chaud.readers.sync();
         (void)h->chagc.readers.sync();
         (void)h->chnb.readers.sync();
+        (void)h->chsq.readers.sync();
         if (h->d_tables) (void)hipFree(h->d_tables);
         for (auto &sl : h->hs) {
             if (sl.d_in) (void)hipFree(sl.d_in);
@@ -1004,6 +1065,7 @@ int sddc_ddc_destroy(sddc_ddc_t *h)
         h->chaud.free_all();
         h->chagc.free_all();
         h->chnb.free_all();
+        h->chsq.free_all();
         if (h->fsa.h_ring) (void)hipHostFree(h->fsa.h_ring);   // its writers were waited for above
         h->readers.clear();
         h->ch_readers.clear();
@@ -1559,6 +1621,15 @@ int sddc_ddc_internal_set_param(sddc_ddc_t *h, int param, int value)
         if (value < 0 || value > (1 << 20))
             return fail(SDDC_ERR_ARG, "channel blanker run length %d outside 0..2^20 blocks", value);
         h->chnb.run_blocks = value;
+        return SDDC_OK;
+    case SDDC_DDC_PARAM_CHSQ_MAX_WGS:
+        if (value < 0) return fail(SDDC_ERR_ARG, "channel squelch workgroup cap %d is negative", value);
+        h->chsq.max_wgs = value;
+        return SDDC_OK;
+    case SDDC_DDC_PARAM_CHSQ_RUN_BLOCKS:
+        if (value < 0 || value > (1 << 20))
+            return fail(SDDC_ERR_ARG, "channel squelch run length %d outside 0..2^20 blocks", value);
+        h->chsq.run_blocks = value;
         return SDDC_OK;
     default:
         return fail(SDDC_ERR_ARG, "unknown parameter %d", param);
@@ -3304,6 +3375,300 @@ int sddc_ddc_channel_blank_host(sddc_ddc_t *h, const void *iq, int nch, size_t n
             HIP_TRY(hipMemcpy2DAsync(out, out_stride * comp, st.d_out, out_stride * comp, 2 * nsamp * comp, (size_t)nch,
                                      hipMemcpyDeviceToHost, h->stream));
         if (count) HIP_TRY(hipMemcpyAsync(count, st.d_count, (size_t)nch * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(h->stream));   // also after a failed launch: the caller's input is free again
+    return rc;
+}
+
+/* ---- channel squelch: a streaming per-channel gate on the audio ------------------------------ */
+static_assert(SDDC_DDC_SQUELCH_BLOCK == sddc::squelch::kSquelchBlock && SDDC_DDC_SQUELCH_OFF == sddc::squelch::kSquelchOff &&
+                  SDDC_DDC_SQUELCH_LEVEL == sddc::squelch::kSquelchLevel && SDDC_DDC_SQUELCH_NOISE == sddc::squelch::kSquelchNoise &&
+                  SDDC_DDC_SQUELCH_MUTE == sddc::squelch::kSquelchMute && SDDC_DDC_SQUELCH_SENSE_SELF == sddc::squelch::kSenseSelf &&
+                  SDDC_DDC_SQUELCH_SENSE_F32 == sddc::squelch::kSenseF32 && SDDC_DDC_SQUELCH_SENSE_S16 == sddc::squelch::kSenseS16 &&
+                  SDDC_DDC_SQUELCH_SENSE_CF32 == sddc::squelch::kSenseCF32 && SDDC_DDC_SQUELCH_SENSE_CS16 == sddc::squelch::kSenseCS16 &&
+                  SDDC_DDC_SQUELCH_MAX_ATTACK == sddc::squelch::kSquelchMaxAttack &&
+                  SDDC_DDC_SQUELCH_MAX_HANG == sddc::squelch::kSquelchMaxHang,
+              "the arithmetic header's constants are the ABI's");
+
+int sddc_ddc_squelch_blocks(double seconds, double fs, int *blocks)
+{
+    if (!blocks) return fail(SDDC_ERR_ARG, "squelch_blocks: null blocks");
+    if (!std::isfinite(seconds) || !std::isfinite(fs) || !(fs > 0.0))
+        return fail(SDDC_ERR_ARG, "squelch_blocks: %g s at %g Hz is not a finite time at a positive rate", seconds, fs);
+    const double b = std::nearbyint(seconds * fs / (double)SDDC_DDC_SQUELCH_BLOCK);
+    if (!(b >= 0.0 && b <= (double)SDDC_DDC_SQUELCH_MAX_HANG))
+        return fail(SDDC_ERR_ARG, "squelch_blocks: %g s at %g Hz is %g blocks, outside 0..%d", seconds, fs, b,
+                    SDDC_DDC_SQUELCH_MAX_HANG);
+    *blocks = (int)b;
+    return SDDC_OK;
+}
+
+int sddc_ddc_set_channel_squelch(sddc_ddc_t *h, const int *modes, const float *thresholds, int nch, int attack, int hang,
+                                 int fade, int sense, int in_format, int out_format)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    const bool off = !modes || !thresholds || nch == 0;
+    std::vector<int> md;
+    std::vector<float> thr;
+    if (!off) {
+        if (nch < 1 || nch > SDDC_DDC_MAX_CHANNELS)
+            return fail(SDDC_ERR_ARG, "channel squelch: nch %d outside 1..%d", nch, SDDC_DDC_MAX_CHANNELS);
+        if (attack < 1 || attack > SDDC_DDC_SQUELCH_MAX_ATTACK)
+            return fail(SDDC_ERR_ARG, "channel squelch: attack %d outside 1..%d blocks", attack, SDDC_DDC_SQUELCH_MAX_ATTACK);
+        if (hang < 0 || hang > SDDC_DDC_SQUELCH_MAX_HANG)
+            return fail(SDDC_ERR_ARG, "channel squelch: hang %d outside 0..%d blocks", hang, SDDC_DDC_SQUELCH_MAX_HANG);
+        if (fade != 0 && fade != 1) return fail(SDDC_ERR_ARG, "channel squelch: fade %d is neither 0 nor 1", fade);
+        if (sense < SDDC_DDC_SQUELCH_SENSE_SELF || sense > SDDC_DDC_SQUELCH_SENSE_CS16)
+            return fail(SDDC_ERR_ARG, "channel squelch: unknown sense kind %d", sense);
+        for (int fmt : {in_format, out_format})
+            if (fmt != SDDC_DDC_AUDIO_F32 && fmt != SDDC_DDC_AUDIO_S16)
+                return fail(SDDC_ERR_ARG, "channel squelch: unknown sample format %d", fmt);
+        const float tmax = 1208925819614629174706176.f;   // 2^80
+        for (int c = 0; c < nch; c++) {
+            const int m = modes[c];
+            const float to = thresholds[2 * c], tc = thresholds[2 * c + 1];
+            if (m < SDDC_DDC_SQUELCH_OFF || m > SDDC_DDC_SQUELCH_MUTE)
+                return fail(SDDC_ERR_ARG, "channel squelch: unknown mode %d of channel %d", m, c);
+            if (!std::isfinite(to) || !std::isfinite(tc) || !(to >= 0.f && to <= tmax) || !(tc >= 0.f && tc <= tmax))
+                return fail(SDDC_ERR_ARG, "channel squelch: a threshold of channel %d is not a finite value in [0, 2^80]", c);
+            if (m == SDDC_DDC_SQUELCH_LEVEL && !(tc <= to))
+                return fail(SDDC_ERR_ARG, "channel squelch: LEVEL channel %d has T_close %g above T_open %g", c, (double)tc, (double)to);
+            if (m == SDDC_DDC_SQUELCH_NOISE && !(tc >= to))
+                return fail(SDDC_ERR_ARG, "channel squelch: NOISE channel %d has T_close %g below T_open %g", c, (double)tc, (double)to);
+        }
+        try {
+            md.assign(modes, modes + nch);
+            thr.resize((size_t)nch * 2);
+        } catch (const std::exception &ex) {
+            return fail(SDDC_ERR_NOMEM, "channel squelch: %s", ex.what());
+        }
+        for (size_t i = 0; i < thr.size(); i++) thr[i] = sddc::squelch::squelch_scale(thresholds[i] == 0.f ? 0.f : thresholds[i]);
+    }
+    std::lock_guard<std::mutex> lk(h->mu);
+    ChannelSquelch &st = h->chsq;
+    if (h->cpu) {
+        st.clear();
+        if (off) return SDDC_OK;
+        try {
+            st.state_h.assign((size_t)nch, sddc::cpu::R2iq::SquelchChannel());
+        } catch (const std::exception &ex) {
+            st.clear();
+            return fail(SDDC_ERR_NOMEM, "channel squelch: %s", ex.what());
+        }
+    } else {
+        DeviceGuard g(h->device);
+        HIP_TRY(g.err);
+        HIP_TRY(st.readers.sync());   // earlier launches, on any stream, may still use the state
+        st.clear();                   // a failed upload leaves the stage off
+        if (off) return SDDC_OK;
+        const size_t nstate = (size_t)nch * sddc::kSquelchStateWords;
+        hipError_t e = hipMalloc(&st.d_modes, md.size() * sizeof(int));
+        if (e == hipSuccess) e = hipMalloc(&st.d_thr, thr.size() * sizeof(float));
+        for (uint32_t *&p : st.d_state)
+            if (e == hipSuccess) e = hipMalloc(&p, nstate * sizeof(uint32_t));
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            st.clear();
+            return fail(SDDC_ERR_NOMEM, "channel squelch: no device memory for %d channels", nch);
+        }
+        e = hipMemcpy(st.d_modes, md.data(), md.size() * sizeof(int), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(st.d_thr, thr.data(), thr.size() * sizeof(float), hipMemcpyHostToDevice);
+        // zeroed on the handle's stream and waited for: the first launch may be on any stream
+        for (uint32_t *p : st.d_state)
+            if (e == hipSuccess) e = hipMemsetAsync(p, 0, nstate * sizeof(uint32_t), h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) {
+            st.clear();
+            HIP_TRY(e);
+        }
+    }
+    st.modes = std::move(md);
+    st.thr = std::move(thr);
+    st.nch = nch;
+    st.attack = attack;
+    st.hang = hang;
+    st.fade = fade;
+    st.sense = sense;
+    st.in_fmt = in_format;
+    st.out_fmt = out_format;
+    st.pos = 0;
+    return SDDC_OK;
+}
+
+int sddc_ddc_channel_squelch_reset(sddc_ddc_t *h)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    ChannelSquelch &st = h->chsq;
+    if (st.modes.empty()) return fail(SDDC_ERR_STATE, "channel squelch reset: no squelch set");
+    if (h->cpu) {
+        std::fill(st.state_h.begin(), st.state_h.end(), sddc::cpu::R2iq::SquelchChannel());
+    } else {
+        DeviceGuard g(h->device);
+        HIP_TRY(g.err);
+        HIP_TRY(st.readers.sync());   // earlier launches, on any stream, may still use the state
+        HIP_TRY(hipMemsetAsync(st.d_state[st.cur], 0, st.state_words() * sizeof(uint32_t), h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));   // the next launch may be on any stream
+    }
+    st.pos = 0;
+    return SDDC_OK;
+}
+
+namespace {
+// the bytes of a sense sample (SELF: 0) and the components per sample
+struct SenseShape {
+    size_t comp, per;
+};
+SenseShape sense_shape(int kind)
+{
+    switch (kind) {
+    case SDDC_DDC_SQUELCH_SENSE_F32: return {4, 1};
+    case SDDC_DDC_SQUELCH_SENSE_S16: return {2, 1};
+    case SDDC_DDC_SQUELCH_SENSE_CF32: return {4, 2};
+    case SDDC_DDC_SQUELCH_SENSE_CS16: return {2, 2};
+    default: return {0, 1};
+    }
+}
+}  // namespace
+
+// the checks both calls share (under h->mu)
+static int check_chsq_args(const sddc_ddc_t *h, const void *in, const void *sense, int nch, size_t nsamp, size_t in_stride,
+                           size_t sense_stride, const void *out, size_t out_stride, const void *open, const void *count,
+                           const void *level)
+{
+    const ChannelSquelch &st = h->chsq;
+    if (st.modes.empty()) return fail(SDDC_ERR_STATE, "channel squelch: no squelch set");
+    if (nch != st.nch)
+        return fail(SDDC_ERR_STATE, "channel squelch: the squelch is set for %d channels, the call has %d", st.nch, nch);
+    if (nsamp == 0 || nsamp > ((size_t)1 << 40)) return fail(SDDC_ERR_ARG, "nsamp must be in 1..2^40 (got %zu)", nsamp);
+    if (nch > 1 && in_stride < nsamp) return fail(SDDC_ERR_ARG, "in_stride must be >= nsamp (got %zu, nsamp %zu)", in_stride, nsamp);
+    if (nch > 1 && out_stride < nsamp)
+        return fail(SDDC_ERR_ARG, "out_stride must be >= nsamp (got %zu, nsamp %zu)", out_stride, nsamp);
+    if (!in || !out) return fail(SDDC_ERR_ARG, "null buffer");
+    const uintptr_t is = st.in_fmt == SDDC_DDC_AUDIO_S16 ? 2 : 4, os = st.out_fmt == SDDC_DDC_AUDIO_S16 ? 2 : 4;
+    if (((uintptr_t)in & (is - 1)) != 0) return fail(SDDC_ERR_ARG, "the input must be %d-byte aligned", (int)is);
+    if (((uintptr_t)out & (os - 1)) != 0) return fail(SDDC_ERR_ARG, "the output must be %d-byte aligned", (int)os);
+    if ((((uintptr_t)open | (uintptr_t)count | (uintptr_t)level) & 3) != 0)
+        return fail(SDDC_ERR_ARG, "the side outputs must be 4-byte aligned");
+    const uintptr_t ia = (uintptr_t)in, oa = (uintptr_t)out;
+    const uintptr_t ib = ia + ((uintptr_t)(nch - 1) * (nch > 1 ? in_stride : 0) + nsamp) * is;
+    const uintptr_t ob = oa + ((uintptr_t)(nch - 1) * (nch > 1 ? out_stride : 0) + nsamp) * os;
+    if (ia < ob && oa < ib) return fail(SDDC_ERR_ARG, "the input and the output overlap");
+    if (st.sense != SDDC_DDC_SQUELCH_SENSE_SELF) {
+        const SenseShape sh = sense_shape(st.sense);
+        if (!sense) return fail(SDDC_ERR_ARG, "null sense buffer with a sense kind other than SELF");
+        if (nch > 1 && (sense_stride < sh.per * nsamp || (sense_stride & (sh.per - 1)) != 0))
+            return fail(SDDC_ERR_ARG, "sense_stride must be %s>= %zu (got %zu)", sh.per == 2 ? "even and " : "", sh.per * nsamp,
+                        sense_stride);
+        if (((uintptr_t)sense & (sh.comp * sh.per - 1)) != 0)
+            return fail(SDDC_ERR_ARG, "the sense buffer must be %d-byte aligned", (int)(sh.comp * sh.per));
+        const uintptr_t sa = (uintptr_t)sense;
+        const uintptr_t sb = sa + ((uintptr_t)(nch - 1) * (nch > 1 ? sense_stride : 0) + sh.per * nsamp) * sh.comp;
+        if (sa < ob && oa < sb) return fail(SDDC_ERR_ARG, "the sense buffer and the output overlap");
+    }
+    return SDDC_OK;
+}
+
+// The call in launch sets of at most run_blocks blocks per channel (the scratch holds a word per channel
+// and block of a set, and the kernels index a set with an int), three kernels each on s.
+static int chsq_launch(sddc_ddc_t *h, const void *d_in, const void *d_sense, int nch, size_t nsamp, size_t in_stride,
+                       size_t sense_stride, void *d_out, size_t out_stride, uint32_t *d_open, uint32_t *d_count, float *d_level,
+                       hipStream_t s)
+{
+    ChannelSquelch &st = h->chsq;
+    const size_t B = SDDC_DDC_SQUELCH_BLOCK, run_blocks = (size_t)(st.run_blocks > 0 ? st.run_blocks : ChannelSquelch::kDefaultRunBlocks);
+    const size_t hb0 = (size_t)(st.pos % B), blocks = (hb0 + nsamp + B - 1) / B;
+    const size_t need = (size_t)nch * (blocks < run_blocks ? blocks : run_blocks);
+    if (need > st.words_cap) {
+        HIP_TRY(st.readers.sync());   // an earlier launch may still use the scratch
+        if (int rc = grow_device_buffer(&st.d_words, &st.words_cap, need, "channel squelch", "scratch words")) return rc;
+    }
+    HIP_TRY(st.readers.order_before(s));
+    const bool in16 = st.in_fmt == SDDC_DDC_AUDIO_S16, out16 = st.out_fmt == SDDC_DDC_AUDIO_S16;
+    const size_t is = in16 ? 2 : 4, os = out16 ? 2 : 4;
+    const SenseShape sh = sense_shape(st.sense);
+    hipError_t e = hipSuccess;
+    for (size_t done = 0; done < nsamp && e == hipSuccess;) {
+        const size_t hb = (size_t)(st.pos % B);
+        size_t n = nsamp - done;
+        if (n > run_blocks * B - hb) n = run_blocks * B - hb;
+        e = sddc::launch_channel_squelch(h->tables, static_cast<const char *>(d_in) + done * is, in16,
+                                         d_sense ? static_cast<const char *>(d_sense) + done * sh.per * sh.comp : nullptr, st.sense,
+                                         nch, n, in_stride, sense_stride, st.pos, st.d_modes, st.d_thr, st.attack, st.hang, st.fade,
+                                         st.d_state[st.cur], st.d_state[st.cur ^ 1], st.d_words,
+                                         static_cast<char *>(d_out) + done * os, out16, out_stride, d_open, d_count, d_level,
+                                         done > 0, st.max_wgs, h->device, s);
+        if (e != hipSuccess) break;
+        st.cur ^= 1;
+        st.pos += n;
+        done += n;
+    }
+    const hipError_t er = st.readers.record(s);   // whatever was enqueued stays ordered
+    HIP_TRY(e);
+    HIP_TRY(er);
+    return SDDC_OK;
+}
+
+int sddc_ddc_channel_squelch_device(sddc_ddc_t *h, const void *d_audio, const void *d_sense, int nch, size_t nsamp,
+                                    size_t in_stride, size_t sense_stride, void *d_out, size_t out_stride, uint32_t *d_open,
+                                    uint32_t *d_count, float *d_level, void *hip_stream)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->cpu) return fail(SDDC_ERR_STATE, "channel_squelch_device: a CPU handle has no device path");
+    if (int rc = check_chsq_args(h, d_audio, d_sense, nch, nsamp, in_stride, sense_stride, d_out, out_stride, d_open, d_count, d_level))
+        return rc;
+    DeviceGuard g(h->device);
+    HIP_TRY(g.err);
+    return chsq_launch(h, d_audio, h->chsq.sense == SDDC_DDC_SQUELCH_SENSE_SELF ? nullptr : d_sense, nch, nsamp, in_stride,
+                       sense_stride, d_out, out_stride, d_open, d_count, d_level, (hipStream_t)hip_stream);
+}
+
+int sddc_ddc_channel_squelch_host(sddc_ddc_t *h, const void *audio, const void *sense, int nch, size_t nsamp,
+                                  size_t in_stride, size_t sense_stride, void *out, size_t out_stride, uint32_t *open,
+                                  uint32_t *count, float *level)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (int rc = check_chsq_args(h, audio, sense, nch, nsamp, in_stride, sense_stride, out, out_stride, open, count, level)) return rc;
+    ChannelSquelch &st = h->chsq;
+    const bool in16 = st.in_fmt == SDDC_DDC_AUDIO_S16, out16 = st.out_fmt == SDDC_DDC_AUDIO_S16;
+    const bool self = st.sense == SDDC_DDC_SQUELCH_SENSE_SELF;
+    if (h->cpu) {
+        sddc::cpu::R2iq::channel_squelch(audio, in16, self ? nullptr : sense, st.sense, nch, nsamp, nch > 1 ? in_stride : 0,
+                                         nch > 1 ? sense_stride : 0, st.modes.data(), st.thr.data(), st.attack, st.hang, st.fade,
+                                         st.pos, st.state_h.data(), out, out16, nch > 1 ? out_stride : 0, open, count, level);
+        st.pos += nsamp;
+        return SDDC_OK;
+    }
+    DeviceGuard g(h->device);
+    HIP_TRY(g.err);
+    // the spans that hold every channel's samples and outputs
+    const size_t is = in16 ? 2 : 4, os = out16 ? 2 : 4;
+    const SenseShape sh = sense_shape(st.sense);
+    const size_t in_bytes = ((size_t)(nch - 1) * (nch > 1 ? in_stride : 0) + nsamp) * is;
+    const size_t out_bytes = ((size_t)(nch - 1) * (nch > 1 ? out_stride : 0) + nsamp) * os;
+    const size_t sense_bytes = self ? 0 : ((size_t)(nch - 1) * (nch > 1 ? sense_stride : 0) + sh.per * nsamp) * sh.comp;
+    if (int rc = grow_device_buffer(&st.d_in, &st.in_cap, in_bytes, "channel_squelch_host", "input bytes")) return rc;
+    if (int rc = grow_device_buffer(&st.d_out, &st.out_cap, out_bytes, "channel_squelch_host", "output bytes")) return rc;
+    if (!self)
+        if (int rc = grow_device_buffer(&st.d_sense, &st.sense_cap, sense_bytes, "channel_squelch_host", "sense bytes")) return rc;
+    if (int rc = grow_device_buffer(&st.d_side, &st.side_cap, (size_t)3 * nch, "channel_squelch_host", "side outputs")) return rc;
+    uint32_t *d_open = open ? st.d_side : nullptr, *d_count = count ? st.d_side + nch : nullptr;
+    float *d_level = level ? reinterpret_cast<float *>(st.d_side + 2 * (size_t)nch) : nullptr;
+    HIP_TRY(hipMemcpyAsync(st.d_in, audio, in_bytes, hipMemcpyHostToDevice, h->stream));
+    if (!self) HIP_TRY(hipMemcpyAsync(st.d_sense, sense, sense_bytes, hipMemcpyHostToDevice, h->stream));
+    const int rc = chsq_launch(h, st.d_in, self ? nullptr : st.d_sense, nch, nsamp, in_stride, sense_stride, st.d_out, out_stride,
+                               d_open, d_count, d_level, h->stream);
+    if (rc == SDDC_OK) {   // the streams alone: the caller's memory between them stays as it is
+        if (nch == 1 || out_stride == nsamp)
+            HIP_TRY(hipMemcpyAsync(out, st.d_out, out_bytes, hipMemcpyDeviceToHost, h->stream));
+        else
+            HIP_TRY(hipMemcpy2DAsync(out, out_stride * os, st.d_out, out_stride * os, nsamp * os, (size_t)nch,
+                                     hipMemcpyDeviceToHost, h->stream));
+        if (open) HIP_TRY(hipMemcpyAsync(open, d_open, (size_t)nch * 4, hipMemcpyDeviceToHost, h->stream));
+        if (count) HIP_TRY(hipMemcpyAsync(count, d_count, (size_t)nch * 4, hipMemcpyDeviceToHost, h->stream));
+        if (level) HIP_TRY(hipMemcpyAsync(level, d_level, (size_t)nch * 4, hipMemcpyDeviceToHost, h->stream));
     }
     HIP_TRY(hipStreamSynchronize(h->stream));   // also after a failed launch: the caller's input is free again
     return rc;

@@ -105,6 +105,16 @@ extern "C" {
  * size, 32..128.  The run length changes no output bit and no count (tests). */
 #define SDDC_DDC_PARAM_CHNB_RUN_BLOCKS 22
 
+/* SDDC_DDC_PARAM_CHSQ_MAX_WGS = n > 0: each of the channel squelch's three grids is at most n workgroups,
+ * as param 21 for the blanker; 0 (default): full residency with a loop.  The grid changes no output bit and
+ * no side output (tests). */
+#define SDDC_DDC_PARAM_CHSQ_MAX_WGS 23
+
+/* SDDC_DDC_PARAM_CHSQ_RUN_BLOCKS = n in 1..2^20: a call of the channel squelch is cut into launch sets of at
+ * most n blocks per channel (the scratch holds one word per channel and block of a set); 0: 4096.  The run
+ * length changes no output bit and no side output (tests). */
+#define SDDC_DDC_PARAM_CHSQ_RUN_BLOCKS 24
+
 int sddc_ddc_internal_set_param(sddc_ddc_t *h, int param, int value);
 /* A given table of n relative shares (n = the d = 0 kernel's full-residency grid, 4 x CUs) used as
  * it is, without clamps or measurements, until n = 0 clears it (tests). */

@@ -180,6 +180,20 @@ def blanker_threshold(db: float) -> float:
     return float(k2.value)
 
 
+SQUELCH_BLOCK = 256                       # SDDC_DDC_SQUELCH_BLOCK: the squelch's block length B
+SQUELCH_OFF, SQUELCH_LEVEL, SQUELCH_NOISE, SQUELCH_MUTE = 0, 1, 2, 3   # SDDC_DDC_SQUELCH_*: a channel's mode
+# SDDC_DDC_SQUELCH_SENSE_*: what the level is measured on
+SQUELCH_SENSE_SELF, SQUELCH_SENSE_F32, SQUELCH_SENSE_S16, SQUELCH_SENSE_CF32, SQUELCH_SENSE_CS16 = 0, 1, 2, 3, 4
+
+
+def squelch_blocks(seconds: float, fs: float) -> int:
+    """An attack or a hang of `seconds` at the audio rate fs in blocks of 256 samples, rounded; 0..65535
+    (sddc_ddc_squelch_blocks)."""
+    b = ctypes.c_int()
+    check(_lib.load().sddc_ddc_squelch_blocks(float(seconds), float(fs), ctypes.addressof(b)))
+    return int(b.value)
+
+
 def psd_to_dbfs(psd) -> np.ndarray:
     """R2iq.spectrum's output in dB relative to a full-scale real tone (amplitude 32768 reads
     32768^2 / 4 at its bin centre): 10 log10(4 psd / 32768^2); -inf where psd is 0."""
@@ -212,6 +226,7 @@ class R2iq:
         self._audio = None   # (nch, in_format, out_format) of setChannelAudioFilter
         self._agc = None     # (nch, in_format, out_format) of setChannelAgc
         self._blanker = None  # (nch, format) of setChannelBlanker
+        self._squelch = None  # (nch, sense, in_format, out_format) of setChannelSquelch
 
     # -- lifecycle --------------------------------------------------------
     @property
@@ -897,6 +912,119 @@ class R2iq:
         check(self._L.sddc_ddc_channel_blank_device(self._h, d_iq.data_ptr(), nch, nsamp, in_stride, d_out.data_ptr(),
                                                     out_stride, None if d_count is None else d_count.data_ptr(),
                                                     _stream_handle(stream)))
+
+    # -- channel squelch --------------------------------------------------------
+    def setChannelSquelch(self, modes, thresholds, attack: int = 1, hang: int = 0, fade: int = 0,
+                          sense: int = SQUELCH_SENSE_SELF, fmt_in: int = AUDIO_F32, fmt_out: int = AUDIO_F32) -> None:
+        """The streaming gate of channel_squelch: modes is int [nch] (SQUELCH_OFF: always open, _LEVEL: opens on
+        a high level, _NOISE: opens on a low level, _MUTE: always closed); thresholds float32 [nch, 2] = (T_open,
+        T_close) as mean squares per sample of the sense stream (LEVEL: T_close <= T_open, NOISE: T_close >=
+        T_open).  attack: 1..255 blocks of 256 samples above T_open before a channel opens; hang: 0..65535
+        blocks it stays open below T_close (squelch_blocks); fade: 1 ramps the opening and the closing block;
+        sense: SQUELCH_SENSE_*, what the level is measured on; fmt_in / fmt_out: AUDIO_F32 or AUDIO_S16.
+        Every call zeroes the state and the stream position.  modes=None turns the stage off."""
+        if modes is None or np.size(modes) == 0:
+            check(self._L.sddc_ddc_set_channel_squelch(self._h, None, None, 0, 0, 0, 0, 0, 0, 0))
+            self._squelch = None
+            return
+        m = np.ascontiguousarray(np.asarray(modes, np.int32).reshape(-1))
+        t = np.ascontiguousarray(np.asarray(thresholds, np.float32))
+        if t.ndim != 2 or t.shape != (m.shape[0], 2):
+            raise DDCError(-1, "thresholds must be [nch, 2] with one row per mode")
+        check(self._L.sddc_ddc_set_channel_squelch(self._h, m.ctypes.data, t.ctypes.data, m.shape[0], int(attack), int(hang),
+                                                   int(fade), int(sense), int(fmt_in), int(fmt_out)))
+        self._squelch = (m.shape[0], int(sense), int(fmt_in), int(fmt_out))
+
+    def resetChannelSquelch(self) -> None:
+        """Zero every channel's state and the stream position: the next call starts a closed stream."""
+        check(self._L.sddc_ddc_channel_squelch_reset(self._h))
+
+    def channel_squelch(self, x: np.ndarray, sense=None, open: bool = True, count: bool = False, level: bool = False):  # noqa: A002
+        """The squelch on a host array: x is float32 (AUDIO_S16 in: int16) [nch, nsamp], any nsamp >= 1; a
+        single stream may drop the channel axis.  sense: the sense stream of the set kind with the same
+        nsamp: float32 or int16 [nch, nsamp], complex64 [nch, nsamp] (SENSE_CF32) or int16 [nch, nsamp, 2]
+        (SENSE_CS16); ignored with SENSE_SELF.  Returns float32 (AUDIO_S16 out: int16) [nch, nsamp], followed
+        by each side output that is asked for: open (uint32 [nch], `open` after the last completed block),
+        count (uint32 [nch], this call's samples in open blocks), level (float32 [nch], the last block level);
+        with none of them the outputs alone.  Keeps every channel's state for the next call."""
+        if self._squelch is None:
+            raise DDCError(-4, "no channel squelch set")
+        nch, kind, fin, fout = self._squelch
+        x = np.asarray(x, np.int16 if fin == AUDIO_S16 else np.float32)
+        if x.ndim == 1:
+            x = x[None, :]
+        x = np.ascontiguousarray(x)
+        if x.ndim != 2 or x.shape[1] < 1:
+            raise DDCError(-1, "x must be [nch, nsamp] with nsamp >= 1")
+        nsamp = x.shape[1]
+        sp, sstride = None, 0
+        if kind != SQUELCH_SENSE_SELF:
+            if sense is None:
+                raise DDCError(-1, "this sense kind needs a sense stream")
+            cplx = kind in (SQUELCH_SENSE_CF32, SQUELCH_SENSE_CS16)
+            s = np.asarray(sense, {SQUELCH_SENSE_F32: np.float32, SQUELCH_SENSE_S16: np.int16,
+                                   SQUELCH_SENSE_CF32: np.complex64, SQUELCH_SENSE_CS16: np.int16}[kind])
+            if s.ndim == (2 if kind == SQUELCH_SENSE_CS16 else 1):
+                s = s[None]
+            s = np.ascontiguousarray(s)
+            if s.shape[:2] != x.shape or s.shape[2:] != ((2,) if kind == SQUELCH_SENSE_CS16 else ()):
+                raise DDCError(-1, "the sense stream must have the audio's [nch, nsamp]")
+            sp, sstride = s.ctypes.data, (2 if cplx else 1) * nsamp
+        out = np.empty((x.shape[0], nsamp), np.int16 if fout == AUDIO_S16 else np.float32)
+        o = np.empty(x.shape[0], np.uint32) if open else None
+        c = np.empty(x.shape[0], np.uint32) if count else None
+        lv = np.empty(x.shape[0], np.float32) if level else None
+        check(self._L.sddc_ddc_channel_squelch_host(self._h, x.ctypes.data, sp, x.shape[0], nsamp, nsamp, sstride,
+                                                    out.ctypes.data, nsamp, *(None if a is None else a.ctypes.data
+                                                                              for a in (o, c, lv))))
+        side = tuple(a for a in (o, c, lv) if a is not None)
+        return (out,) + side if side else out
+
+    def channel_squelch_device(self, d_audio, d_sense, nch: int, nsamp: int, in_stride: int, sense_stride: int, d_out,
+                               out_stride: int, d_open=None, d_count=None, d_level=None, stream=None) -> None:
+        """The squelch on the buffer channel_demodulate_device, channel_audio_filter_device or
+        channel_agc_device wrote: d_audio is a float32 (AUDIO_S16 in: int16) device tensor, channel c's nsamp
+        samples at c * in_stride; d_sense the sense stream of the set kind (float32 or int16 components,
+        channel c's at c * sense_stride components; None with SENSE_SELF); d_out float32 (AUDIO_S16 out:
+        int16), channel c's outputs at c * out_stride; d_out must overlap neither input.  d_open, d_count:
+        None or int32 device tensors of nch values; d_level: None or a float32 one.  Enqueued on `stream`
+        like process_device; the calls of one handle run in call order."""
+        import torch
+        if self._squelch is None:
+            raise DDCError(-4, "no channel squelch set")
+        _, kind, fin, fout = self._squelch
+        if nch < 1 or nsamp < 1:
+            raise DDCError(-1, "nch and nsamp must be >= 1")
+        if kind == SQUELCH_SENSE_SELF:
+            d_sense = None
+        elif d_sense is None:
+            raise DDCError(-1, "this sense kind needs d_sense")
+        sides = (("d_open", d_open, torch.int32), ("d_count", d_count, torch.int32), ("d_level", d_level, torch.float32))
+        if not all(t is None or t.is_cuda for t in (d_audio, d_out, d_sense, d_open, d_count, d_level)):
+            raise DDCError(-1, "device path needs device tensors")
+        want = torch.int16 if fin == AUDIO_S16 else torch.float32
+        want_out = torch.int16 if fout == AUDIO_S16 else torch.float32
+        if d_audio.dtype != want or d_out.dtype != want_out:
+            raise DDCError(-1, f"d_audio must be {want} and d_out {want_out}")
+        bufs = [("d_audio", d_audio, in_stride, 1), ("d_out", d_out, out_stride, 1)]
+        if d_sense is not None:
+            want_s = torch.int16 if kind in (SQUELCH_SENSE_S16, SQUELCH_SENSE_CS16) else torch.float32
+            if d_sense.dtype != want_s:
+                raise DDCError(-1, f"d_sense must be {want_s}")
+            bufs.append(("d_sense", d_sense, sense_stride, 2 if kind in (SQUELCH_SENSE_CF32, SQUELCH_SENSE_CS16) else 1))
+        for name, t, stride, per in bufs:
+            if not t.is_contiguous():
+                raise DDCError(-1, "tensors must be contiguous")
+            need = (nch - 1) * stride + per * nsamp
+            if t.numel() < need:
+                raise DDCError(-1, f"{name} has {t.numel()} components, need {need}")
+        for name, t, dt in sides:
+            if t is not None and (t.dtype != dt or not t.is_contiguous() or t.numel() < nch):
+                raise DDCError(-1, f"{name} must be a contiguous {dt} tensor of at least {nch} values")
+        check(self._L.sddc_ddc_channel_squelch_device(self._h, d_audio.data_ptr(), None if d_sense is None else d_sense.data_ptr(),
+                                                      nch, nsamp, in_stride, sense_stride, d_out.data_ptr(), out_stride,
+                                                      *(None if t is None else t.data_ptr() for _, t, _ in sides),
+                                                      _stream_handle(stream)))
 
 
 def _check_device_buffers(d_in, nblk, d_out, out_floats, fmt=0):

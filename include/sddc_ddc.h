@@ -744,6 +744,106 @@ int sddc_ddc_channel_blank_device(sddc_ddc_t *h, const void *d_iq, int nch, size
 int sddc_ddc_channel_blank_host(sddc_ddc_t *h, const void *iq, int nch, size_t nsamp, size_t in_stride, void *out,
                                 size_t out_stride, uint32_t *count);
 
+/* ---- channel squelch: a streaming per-channel gate on the audio --------------------------------
+ * An empty NBFM channel leaves the discriminator as full-scale hiss, and the AGC turns an empty AM or SSB
+ * channel up to its target: the chain yields playable audio only for occupied channels.  The squelch is
+ * the last stage: it gates each channel's audio (the demodulator's, the audio filter's or the AGC's
+ * buffer as it lies) by the level of a sense stream, with an attack, a hang and an optional fade, and it
+ * tells the host which channels are open without moving any audio.  Three uses: a carrier squelch (sense
+ * = the demodulator's IQ input, LEVEL), an FM noise squelch (sense = the discriminator audio through a
+ * high-pass of the audio filter into a second buffer, NOISE) and a plain audio-level gate (SELF).  What
+ * this squelch is NOT: it has no look-ahead (up to A + 1 blocks of a transmission's start are lost), no
+ * tone (CTCSS) decode, and its thresholds do not adapt to the noise floor.
+ *
+ * The definition (normative; csrc/squelch_math.h holds the operations, shared by both backends, float,
+ * contraction off, only *, +, comparisons, selects and integers).  B = SDDC_DDC_SQUELCH_BLOCK = 256; i >= 0
+ * is the stream index since the last set or reset, k = i div B its block.
+ *   Inputs.     The audio: nch x nsamp samples, SDDC_DDC_AUDIO_F32 or _S16 (read as (float)v).  The sense
+ *               stream: nsamp samples per channel at the same rate, of the kind the set call fixes:
+ *               SDDC_DDC_SQUELCH_SENSE_SELF   the audio itself (d_sense ignored)           q = x * x
+ *               .._SENSE_F32 / .._SENSE_S16   a separate real buffer (S16 as (float)v)     q = x * x
+ *               .._SENSE_CF32 / .._SENSE_CS16 the complex buffer the demodulator read      q = (I * I) + (Q * Q)
+ *               (strides in components, even for the complex kinds, as the channel decimator's).
+ *   Block level. p_k: the balanced pairwise tree over the 256 q values of block k in sample order (level 0
+ *               adds (q[0] + q[1]), (q[2] + q[3]), ...; eight levels: the blanker's block power).  A q that
+ *               is not finite (!(q <= FLT_MAX)) enters as 0 and marks the block bad.
+ *   Per channel. A mode: SDDC_DDC_SQUELCH_OFF (always open, y = x from sample 0), _LEVEL (opens on a high
+ *               level), _NOISE (opens on a low level), _MUTE (always closed); and two thresholds as
+ *               mean-square per sample, T_open and T_close; the set call stores To = 256 T_open, Tc = 256
+ *               T_close (exact).  LEVEL: u_k = p_k > To, v_k = p_k > Tc, and T_close <= T_open.  NOISE:
+ *               u_k = p_k < To, v_k = p_k < Tc, and T_close >= T_open.  A bad block has u = v = false.
+ *   Per handle. The attack A (1..255 blocks), the hang H (0..65535 blocks), fade (0 / 1), the sense kind,
+ *               the audio formats in and out.
+ *   State.      Per channel, integers, all zero on a new stream; after block k:
+ *                   r = u_k ? min(r + 1, A) : 0
+ *                   n = v_k ? 0 : min(n + 1, H + 1)
+ *                   open = open ? (n <= H) : (r >= A)
+ *               (open after k iff the last block ending a run of >= A u-blocks is later than the last block
+ *               ending a run of >= H + 1 non-v blocks.)
+ *   Gate.       G_k = open after block k - 1; G_0 = G_{-1} = 0.  OFF: G = 1 everywhere; MUTE: G = 0.  Block
+ *               k's samples never need block k's level: the stage is causal and has no delay.
+ *   Weight.     Of sample i of block k.  Fade off: w = G_k.  Fade on: w = G_k where G_k = G_{k-1}; on an
+ *               opening block w = (i + 1) / 256, on a closing block w = (255 - i) / 256 (exact floats).
+ *   Output.     w = 1: x unchanged (F32 words and S16 codes bit for bit; S16 to F32 is (float)v, F32 to S16
+ *               the demodulator's conversion).  w = 0: +0.  Otherwise x * w, one rounding, then the
+ *               demodulator's output conversion (round to nearest even, clamp, NaN -> 0).
+ *   Side outputs, each NULL or nch entries: open (uint32): `open` after the last completed block of the
+ *               stream so far (OFF: 1, MUTE: 0); count (uint32, modulo 2^32): the call's output samples
+ *               whose block has G_k = 1, the counts of consecutive calls add up to the count of one call
+ *               over the same samples; level (float): p of the last completed block, 0 before any, also in
+ *               OFF and MUTE: the figure to calibrate thresholds from (divide by 256 for a mean square).
+ * Outputs and side outputs are bit-identical from run to run, for any grid, run length and cut of a
+ * stream into calls, for a channel alone or among others, and between a GPU handle and a CPU handle.
+ * Range of that guarantee: the blanker's: components that are 0 or of magnitude in [2^-40, 2^40],
+ * thresholds finite, >= 0 and <= 2^80.  Outside it both sides perform the same operations, and no value
+ * is a reason for a memory fault.  Against a float64 evaluation of the same definition, u or v of a
+ * block can differ only where |p - T| <= 1.01 * 11 * 2^-24 * T (3 roundings in q, 8 tree levels).
+ * State per handle, on the device for a GPU handle, independent of every other stage's: the position;
+ * per channel r, n, open, G of the block before the unfinished one, the last level and the unfinished
+ * block's q values. */
+#define SDDC_DDC_SQUELCH_BLOCK 256
+#define SDDC_DDC_SQUELCH_OFF 0
+#define SDDC_DDC_SQUELCH_LEVEL 1
+#define SDDC_DDC_SQUELCH_NOISE 2
+#define SDDC_DDC_SQUELCH_MUTE 3
+#define SDDC_DDC_SQUELCH_SENSE_SELF 0
+#define SDDC_DDC_SQUELCH_SENSE_F32 1
+#define SDDC_DDC_SQUELCH_SENSE_S16 2
+#define SDDC_DDC_SQUELCH_SENSE_CF32 3
+#define SDDC_DDC_SQUELCH_SENSE_CS16 4
+#define SDDC_DDC_SQUELCH_MAX_ATTACK 255
+#define SDDC_DDC_SQUELCH_MAX_HANG 65535
+/* blocks = round(seconds * fs / 256): an attack or a hang in blocks.  SDDC_ERR_ARG if the result is outside
+ * 0..65535, an argument is not finite, fs <= 0 or blocks is NULL.  Stateless. */
+int sddc_ddc_squelch_blocks(double seconds, double fs, int *blocks);
+/* modes: host array [nch]; thresholds: host array [nch][2] = (T_open, T_close), finite, >= 0, <= 2^80, in
+ * the order the channel's mode asks for (OFF and MUTE: any order); 1 <= nch <= SDDC_DDC_MAX_CHANNELS; a
+ * violation returns SDDC_ERR_ARG and sets nothing.  modes or thresholds NULL or nch == 0 turns the stage off
+ * and frees its state.  Every set call zeroes the state and the position, and waits for the stage's
+ * launches in flight. */
+int sddc_ddc_set_channel_squelch(sddc_ddc_t *h, const int *modes, const float *thresholds, int nch, int attack, int hang,
+                                 int fade, int sense, int in_format, int out_format);
+/* zero the state and the position: the next call starts a closed stream (SDDC_ERR_STATE: no squelch set) */
+int sddc_ddc_channel_squelch_reset(sddc_ddc_t *h);
+/* GPU handles; enqueued on hip_stream, returns after launch.  Channel c's nsamp audio samples at d_audio +
+ * c * in_stride samples, its sense samples at d_sense + c * sense_stride components (complex kinds: even,
+ * >= 2 nsamp), its outputs at d_out + c * out_stride samples; strides >= nsamp for nch > 1; bases aligned
+ * to a sample (a complex sample for the complex kinds); any 1 <= nsamp <= 2^40.  The output must overlap
+ * neither the audio nor the sense stream; nothing is written between the streams or outside them.
+ * d_open, d_count, d_level: NULL or nch device entries.  SDDC_ERR_STATE: no squelch set, another nch than
+ * the set one, a CPU handle.  SDDC_ERR_ARG: the rest (d_sense NULL with a sense kind other than SELF among
+ * them).  A failed call changes no state.  The calls of one handle share the state and the position: they
+ * run one after the other in call order, whatever their streams. */
+int sddc_ddc_channel_squelch_device(sddc_ddc_t *h, const void *d_audio, const void *d_sense, int nch, size_t nsamp,
+                                    size_t in_stride, size_t sense_stride, void *d_out, size_t out_stride, uint32_t *d_open,
+                                    uint32_t *d_count, float *d_level, void *hip_stream);
+/* Host buffers, the same layouts.  GPU handle: copy in, kernels, copy back, synchronous; it advances the
+ * same device state as the device call.  CPU handle: the definition's loop through the same arithmetic
+ * header. */
+int sddc_ddc_channel_squelch_host(sddc_ddc_t *h, const void *audio, const void *sense, int nch, size_t nsamp,
+                                  size_t in_stride, size_t sense_stride, void *out, size_t out_stride, uint32_t *open,
+                                  uint32_t *count, float *level);
+
 /* ---- ingest ---------------------------------------
  * Pin a caller-owned host region (hipHostRegister) so the host path DMAs blocks
  * from it and output into it directly instead of staging through the library's
