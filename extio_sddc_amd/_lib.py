@@ -97,6 +97,12 @@ SIGNATURES = {
     "sddc_ddc_channel_squelch_reset": (_I, [_P]),
     "sddc_ddc_channel_squelch_device": (_I, [_P, _P, _P, _I, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _P, _P]),
     "sddc_ddc_channel_squelch_host": (_I, [_P, _P, _P, _I, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _P]),
+    "sddc_ddc_tone_window": (_I, [ctypes.c_double, ctypes.c_double, _P]),
+    "sddc_ddc_set_channel_tone_detector": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I]),
+    "sddc_ddc_channel_tone_reset": (_I, [_P]),
+    "sddc_ddc_channel_tone_device": (_I, [_P, _P, _SZ, _P, _I, _SZ, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _P]),
+    "sddc_ddc_channel_tone_host": (_I, [_P, _P, _SZ, _P, _I, _SZ, _SZ, _P, _SZ, _P, _P, _P, _P, _P]),
+    "sddc_ddc_internal_chtone_set_position": (_I, [_P, ctypes.c_uint64]),
     "sddc_ddc_register_host": (_I, [_P, _P, _SZ]),
     "sddc_ddc_unregister_host": (_I, [_P, _P]),
     # include/sddc_fft.h

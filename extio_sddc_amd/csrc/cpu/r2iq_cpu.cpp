@@ -703,5 +703,97 @@ void R2iq::channel_squelch(const void *audio, bool in16, const void *sense, int 
     }
 }
 
+// The channel tone detector: tone_math.h's stream, sample by sample; a block's sums when it completes.
+void R2iq::channel_tone(const void *sense, bool sense16, const void *audio, bool in16, int nch, size_t nsamp,
+                        size_t sense_stride, size_t in_stride, const uint32_t *words, int ntones, const uint64_t *masks,
+                        const float *thr, int window, int attack, int hang, uint64_t pos, ToneChannel *state, void *out,
+                        bool out16, size_t out_stride, int32_t *tone_out, uint32_t *open, uint32_t *count, float *level,
+                        float *powers)
+{
+    using namespace tone;
+    const int B = kToneBlock;
+    // (c_i, s_i) of every tone: they depend on the tone and on i alone
+    std::vector<float> pc((size_t)ntones * B), ps((size_t)ntones * B);
+    for (int t = 0; t < ntones; t++)
+        for (int i = 0; i < B; i++) tone_phasor(words[t], (uint32_t)i, &pc[(size_t)t * B + i], &ps[(size_t)t * B + i]);
+    for (int c = 0; c < nch; c++) {
+        const float *sf = static_cast<const float *>(sense) + (size_t)c * sense_stride;
+        const int16_t *ss = static_cast<const int16_t *>(sense) + (size_t)c * sense_stride;
+        const float *xf = static_cast<const float *>(audio) + (size_t)c * in_stride;
+        const int16_t *xs = static_cast<const int16_t *>(audio) + (size_t)c * in_stride;
+        float *yf = static_cast<float *>(out) + (size_t)c * out_stride;
+        int16_t *ys = static_cast<int16_t *>(out) + (size_t)c * out_stride;
+        const uint64_t mask = masks[c];
+        const float To = thr[3 * c], Tc = thr[3 * c + 1], Emin = thr[3 * c + 2];
+        ToneChannel &st = state[c];
+        int b = (int)(pos % (uint64_t)B);
+        uint64_t k = pos / (uint64_t)B;   // the stream's block index
+        uint32_t cnt = 0;
+        for (size_t i = 0; i < nsamp; i++) {
+            const float s = sense16 ? (float)ss[i] : sf[i];
+            const bool fin = blank::blank_finite(s * s);
+            st.x[b] = fin ? s : 0.f;
+            st.bad |= fin ? 0u : 1u;
+            const uint32_t g = mask == 0 ? 1u : st.open;
+            if (audio) {
+                if (out16) {
+                    ys[i] = g ? demod::demod_s16(in16 ? (float)xs[i] : xf[i]) : (int16_t)0;
+                } else if (!g) {
+                    yf[i] = 0.f;
+                } else if (in16) {
+                    yf[i] = (float)xs[i];
+                } else {
+                    __builtin_memcpy(&yf[i], &xf[i], 4);   // the stored word: a NaN keeps its payload
+                }
+            }
+            cnt += g;
+            if (++b < B) continue;
+            b = 0;
+            float tmp[kToneBlock];
+            for (int m = 0; m < B; m++) tmp[m] = st.x[m] * st.x[m];
+            st.E = st.E + blank::blank_tree(tmp);
+            const uint32_t pos256 = (uint32_t)(k * (uint64_t)B);
+            for (uint64_t mm = mask; mm; mm &= mm - 1) {
+                const int t = __builtin_ctzll(mm);
+                const float *ct = &pc[(size_t)t * B], *sn = &ps[(size_t)t * B];
+                for (int m = 0; m < B; m++) tmp[m] = st.x[m] * ct[m];
+                const float Ck = blank::blank_tree(tmp);
+                for (int m = 0; m < B; m++) tmp[m] = st.x[m] * sn[m];
+                const float Sk = blank::blank_tree(tmp);
+                float cr, sr, re, im;
+                tone_phasor(words[t], pos256, &cr, &sr);
+                tone_rotate(Ck, Sk, cr, sr, &re, &im);
+                st.zr[t] = st.zr[t] + re;
+                st.zi[t] = st.zi[t] + im;
+            }
+            k++;
+            if (k % (uint64_t)window != 0) continue;
+            // the window is complete
+            int best = -1;
+            float Pbest = 0.f;
+            for (int t = 0; t < kToneMaxTones; t++) {
+                const bool in = (mask >> t) & 1;
+                st.pow[t] = in ? blank::blank_power(st.zr[t], st.zi[t]) : 0.f;
+                if (in) tone_best(t, st.pow[t], &best, &Pbest);
+                st.zr[t] = st.zi[t] = 0.f;
+            }
+            bool u, v;
+            tone_flags(Pbest, st.E, st.bad != 0, To, Tc, Emin, &u, &v);
+            squelch::squelch_step(u, v, (uint32_t)attack, (uint32_t)hang, &st.r, &st.n, &st.open);
+            st.tone = v ? best : -1;
+            st.pbest = Pbest;
+            st.elast = st.E;
+            st.E = 0.f;
+            st.bad = 0;
+        }
+        if (tone_out) tone_out[c] = st.tone;
+        if (open) open[c] = mask == 0 ? 1u : st.open;
+        if (count) count[c] = cnt;
+        if (level) level[2 * c] = st.pbest, level[2 * c + 1] = st.elast;
+        if (powers)
+            for (int t = 0; t < ntones; t++) powers[(size_t)c * ntones + t] = st.pow[t];
+    }
+}
+
 }  // namespace cpu
 }  // namespace sddc

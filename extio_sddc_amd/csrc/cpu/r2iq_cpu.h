@@ -28,6 +28,7 @@
 #include "../blanker_math.h"
 #include "../demod_math.h"
 #include "../squelch_math.h"
+#include "../tone_math.h"
 #include "fft_avx2.hpp"
 
 namespace sddc {
@@ -143,6 +144,28 @@ public:
                                 size_t in_stride, size_t sense_stride, const int *modes, const float *thr, int attack,
                                 int hang, int fade, uint64_t pos, SquelchChannel *state, void *out, bool out16,
                                 size_t out_stride, uint32_t *open, uint32_t *count, float *level);
+    // The channel tone detector (sddc_ddc.h, sddc_ddc_channel_tone_host; tone_math.h): the definition's loop,
+    // sample by sample.  Channel c's nsamp sense samples (float, or int16 when sense16) at sense + c *
+    // sense_stride, its audio (null: detect only; float, or int16 when in16) at audio + c * in_stride, its
+    // outputs (float, or int16 when out16) at out + c * out_stride.  words: [ntones]; masks: [nch]; thr:
+    // [nch][3] = (To, Tc, Emin), scaled; window: W; pos: the stream index of the call's first sample; state:
+    // [nch], before the call and replaced by the one after it; tone, open, count: null or [nch]; level: null
+    // or [nch][2]; powers: null or [nch][ntones].
+    struct ToneChannel {
+        uint32_t r = 0, n = 0, open = 0;   // the gate after the last completed window
+        int32_t tone = -1;                 // the last completed window's: the best tone where v held, P_best, E
+        float pbest = 0.f, elast = 0.f;
+        float E = 0.f;                     // the unfinished window's energy, and whether it holds a non-finite q
+        uint32_t bad = 0;
+        float zr[tone::kToneMaxTones] = {}, zi[tone::kToneMaxTones] = {};   // the unfinished window's sums
+        float pow[tone::kToneMaxTones] = {};                                // every P_t of the last completed window
+        float x[tone::kToneBlock] = {};    // the unfinished block's samples, non-finite ones as 0
+    };
+    static void channel_tone(const void *sense, bool sense16, const void *audio, bool in16, int nch, size_t nsamp,
+                             size_t sense_stride, size_t in_stride, const uint32_t *words, int ntones, const uint64_t *masks,
+                             const float *thr, int window, int attack, int hang, uint64_t pos, ToneChannel *state, void *out,
+                             bool out16, size_t out_stride, int32_t *tone, uint32_t *open, uint32_t *count, float *level,
+                             float *powers);
     // demod_math.h's routines on arrays (the accuracy sweeps of tests/test_channel_demod_cpu.py)
     static void demod_angle_n(const float *im, const float *re, size_t n, float *out);
     static void demod_sincos_n(const uint32_t *words, size_t n, float *c, float *s);

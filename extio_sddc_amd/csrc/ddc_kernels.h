@@ -331,6 +331,25 @@ hipError_t launch_channel_squelch(const KernelTables &t, const void *d_audio, in
                                   int out_s16, size_t out_stride, uint32_t *d_open, uint32_t *d_count, float *d_level,
                                   int accumulate, int max_wgs, int device, hipStream_t s);
 
+// Channel tone detector (ddc_channel_tone.hip, sddc_ddc_channel_tone_device): one launch set of the
+// Goertzel bank and its gate (tone_math.h) over nch real sense streams (F32 or S16) and, where d_audio is not
+// null, their audio streams (F32 or S16 in and out); strides in samples.  pos: the stream index of the first
+// sample; nsamp at most kToneMaxLaunch.  d_tones: [ntones] phase words; d_masks: [nch], max_mask_tones: the most tones any of them has (it picks the windows kernel's shape, no
+// bit depends on it); d_thr: [nch][3]
+// floats (To, Tc, Emin); d_state_in / d_state_out: [nch][kToneStateWords] words before / after (two
+// buffers); d_scratch: [nch][windows that hold a sample][4] words; d_tone, d_open, d_count: null or [nch];
+// d_level: null or [nch][2]; d_powers: null or [nch][ntones]; accumulate: d_count holds earlier launches of
+// the same call and is added to.  Two or three launches on s; max_wgs > 0 caps their grids (tests).  The
+// caller has checked the strides and the alignment of the bases to a sample.
+constexpr int kToneStateWords = 456;
+constexpr size_t kToneMaxLaunch = (size_t)1 << 28;
+hipError_t launch_channel_tone(const KernelTables &t, const void *d_sense, int sense_s16, size_t sense_stride, const void *d_audio,
+                               int in_s16, int nch, size_t nsamp, size_t in_stride, uint64_t pos, const uint32_t *d_tones,
+                               int ntones, const uint64_t *d_masks, int max_mask_tones, const float *d_thr, int window, int attack,
+                               int hang, const uint32_t *d_state_in, uint32_t *d_state_out, uint32_t *d_scratch, void *d_out, int out_s16,
+                               size_t out_stride, int *d_tone, uint32_t *d_open, uint32_t *d_count, float *d_level,
+                               float *d_powers, int accumulate, int max_wgs, int device, hipStream_t s);
+
 // batched FFTs (fft_batch.hip, include/sddc_fft.h); fft_prepare fills the device's twiddle
 // table once (synchronises s the first time)
 hipError_t fft_prepare(hipStream_t s);

@@ -499,6 +499,71 @@ struct ChannelSquelch {
     }
 };
 
+// The state of the channel tone detector (sddc_ddc_channel_tone_*; tone_math.h): the tone words [ntones],
+// the masks [nch] and the scaled thresholds [nch][3] = (To, Tc, Emin) (empty = off) with their device copies,
+// the handle's window, attack, hang and formats, the stream position (host) and each channel's state as
+// [nch][kToneStateWords] words in two device buffers that swap per launch set, as ChannelSquelch's do;
+// d_scratch holds four words per channel and window of a launch set, grown on demand.  A CPU handle keeps
+// the state in state_h.  d_sense / d_in / d_out / d_side are the host call's device buffers.  All under the
+// handle's mu.
+struct ChannelTone {
+    static constexpr int kDefaultRunBlocks = 4096;
+    std::vector<uint32_t> words;
+    std::vector<uint64_t> masks;
+    std::vector<float> thr;
+    int nch = 0, ntones = 0, window = 0, attack = 0, hang = 0, sense_fmt = 0, in_fmt = 0, out_fmt = 0;
+    int max_mask_tones = 0;   // the most tones any channel's mask has
+    uint64_t pos = 0;
+    uint32_t *d_tones = nullptr;
+    uint64_t *d_masks = nullptr;
+    float *d_thr = nullptr;
+    uint32_t *d_state[2] = {};
+    int cur = 0;
+    uint32_t *d_scratch = nullptr;
+    size_t scratch_cap = 0;
+    std::vector<sddc::cpu::R2iq::ToneChannel> state_h;
+    Readers readers;
+    int max_wgs = 0, run_blocks = 0;   // SDDC_DDC_PARAM_CHTONE_MAX_WGS, _RUN_BLOCKS (0: kDefaultRunBlocks)
+    void *d_sense = nullptr, *d_in = nullptr, *d_out = nullptr;
+    uint32_t *d_side = nullptr;        // [nch] tone, [nch] open, [nch] count, [nch][2] level, [nch][ntones] powers
+    size_t sense_cap = 0, in_cap = 0, out_cap = 0, side_cap = 0;   // bytes, bytes, bytes, words
+
+    size_t state_words() const { return (size_t)nch * sddc::kToneStateWords; }
+    void clear()
+    {
+        words.clear();
+        masks.clear();
+        thr.clear();
+        nch = ntones = window = attack = hang = sense_fmt = in_fmt = out_fmt = max_mask_tones = 0;
+        pos = 0;
+        state_h.clear();
+        if (d_tones) (void)hipFree(d_tones);
+        if (d_masks) (void)hipFree(d_masks);
+        if (d_thr) (void)hipFree(d_thr);
+        d_tones = nullptr;
+        d_masks = nullptr;
+        d_thr = nullptr;
+        for (uint32_t *&p : d_state) {
+            if (p) (void)hipFree(p);
+            p = nullptr;
+        }
+        cur = 0;
+    }
+    void free_all()
+    {
+        clear();
+        if (d_scratch) (void)hipFree(d_scratch);
+        if (d_sense) (void)hipFree(d_sense);
+        if (d_in) (void)hipFree(d_in);
+        if (d_out) (void)hipFree(d_out);
+        if (d_side) (void)hipFree(d_side);
+        d_scratch = d_side = nullptr;
+        d_sense = d_in = d_out = nullptr;
+        scratch_cap = sense_cap = in_cap = out_cap = side_cap = 0;
+        readers.clear();
+    }
+};
+
 }  // namespace
 
 struct sddc_ddc {
@@ -672,6 +737,7 @@ struct sddc_ddc {
     ChannelAgc chagc;
     ChannelBlanker chnb;
     ChannelSquelch chsq;
+    ChannelTone chtone;
 
     // CPU handle (device SDDC_DDC_DEVICE_CPU): the AVX2 backend; no HIP object above exists
     std::unique_ptr<sddc::cpu::R2iq> cpu;
@@ -1028,6 +1094,7 @@ int sddc_ddc_destroy(sddc_ddc_t *h)
         (void)h->chagc.readers.sync();
         (void)h->chnb.readers.sync();
         (void)h->chsq.readers.sync();
+        (void)h->chtone.readers.sync();
         if (h->d_tables) (void)hipFree(h->d_tables);
         for (auto &sl : h->hs) {
             if (sl.d_in) (void)hipFree(sl.d_in);
@@ -1066,6 +1133,7 @@ int sddc_ddc_destroy(sddc_ddc_t *h)
         h->chagc.free_all();
         h->chnb.free_all();
         h->chsq.free_all();
+        h->chtone.free_all();
         if (h->fsa.h_ring) (void)hipHostFree(h->fsa.h_ring);   // its writers were waited for above
         h->readers.clear();
         h->ch_readers.clear();
@@ -1630,6 +1698,15 @@ int sddc_ddc_internal_set_param(sddc_ddc_t *h, int param, int value)
         if (value < 0 || value > (1 << 20))
             return fail(SDDC_ERR_ARG, "channel squelch run length %d outside 0..2^20 blocks", value);
         h->chsq.run_blocks = value;
+        return SDDC_OK;
+    case SDDC_DDC_PARAM_CHTONE_MAX_WGS:
+        if (value < 0) return fail(SDDC_ERR_ARG, "channel tone detector workgroup cap %d is negative", value);
+        h->chtone.max_wgs = value;
+        return SDDC_OK;
+    case SDDC_DDC_PARAM_CHTONE_RUN_BLOCKS:
+        if (value < 0 || value > (1 << 20))
+            return fail(SDDC_ERR_ARG, "channel tone detector run length %d outside 0..2^20 blocks", value);
+        h->chtone.run_blocks = value;
         return SDDC_OK;
     default:
         return fail(SDDC_ERR_ARG, "unknown parameter %d", param);
@@ -3669,6 +3746,327 @@ int sddc_ddc_channel_squelch_host(sddc_ddc_t *h, const void *audio, const void *
         if (open) HIP_TRY(hipMemcpyAsync(open, d_open, (size_t)nch * 4, hipMemcpyDeviceToHost, h->stream));
         if (count) HIP_TRY(hipMemcpyAsync(count, d_count, (size_t)nch * 4, hipMemcpyDeviceToHost, h->stream));
         if (level) HIP_TRY(hipMemcpyAsync(level, d_level, (size_t)nch * 4, hipMemcpyDeviceToHost, h->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(h->stream));   // also after a failed launch: the caller's input is free again
+    return rc;
+}
+
+/* ---- channel tone detector: streaming per-channel CTCSS / tone squelch ------------------------- */
+static_assert(SDDC_DDC_TONE_BLOCK == sddc::tone::kToneBlock && SDDC_DDC_TONE_MAX_TONES == sddc::tone::kToneMaxTones &&
+                  SDDC_DDC_TONE_MAX_WINDOW == sddc::tone::kToneMaxWindow && SDDC_DDC_TONE_MAX_ATTACK == sddc::tone::kToneMaxAttack &&
+                  SDDC_DDC_TONE_MAX_HANG == sddc::tone::kToneMaxHang,
+              "the arithmetic header's constants are the ABI's");
+static_assert(sizeof(sddc::cpu::R2iq::ToneChannel) == (size_t)sddc::kToneStateWords * 4, "the CPU state holds what the device's does");
+
+int sddc_ddc_tone_window(double seconds, double fs, int *blocks)
+{
+    if (!blocks) return fail(SDDC_ERR_ARG, "tone_window: null blocks");
+    if (!std::isfinite(seconds) || !std::isfinite(fs) || !(fs > 0.0) || !(seconds >= 0.0))
+        return fail(SDDC_ERR_ARG, "tone_window: %g s at %g Hz is not a finite time >= 0 at a positive rate", seconds, fs);
+    double b = std::nearbyint(seconds * fs / (double)SDDC_DDC_TONE_BLOCK);
+    if (b < 1.0) b = 1.0;
+    if (!(b <= (double)SDDC_DDC_TONE_MAX_WINDOW))
+        return fail(SDDC_ERR_ARG, "tone_window: %g s at %g Hz is %g blocks, above %d", seconds, fs, b, SDDC_DDC_TONE_MAX_WINDOW);
+    *blocks = (int)b;
+    return SDDC_OK;
+}
+
+int sddc_ddc_set_channel_tone_detector(sddc_ddc_t *h, const uint32_t *words, int ntones, const uint64_t *masks,
+                                       const float *thresholds, int nch, int window, int attack, int hang, int sense_format,
+                                       int in_format, int out_format)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    const bool off = !words || !masks || !thresholds || nch == 0;
+    std::vector<uint32_t> wd;
+    std::vector<uint64_t> mk;
+    std::vector<float> thr;
+    if (!off) {
+        if (nch < 1 || nch > SDDC_DDC_MAX_CHANNELS)
+            return fail(SDDC_ERR_ARG, "channel tone detector: nch %d outside 1..%d", nch, SDDC_DDC_MAX_CHANNELS);
+        if (ntones < 1 || ntones > SDDC_DDC_TONE_MAX_TONES)
+            return fail(SDDC_ERR_ARG, "channel tone detector: ntones %d outside 1..%d", ntones, SDDC_DDC_TONE_MAX_TONES);
+        if (window < 1 || window > SDDC_DDC_TONE_MAX_WINDOW)
+            return fail(SDDC_ERR_ARG, "channel tone detector: window %d outside 1..%d blocks", window, SDDC_DDC_TONE_MAX_WINDOW);
+        if (attack < 1 || attack > SDDC_DDC_TONE_MAX_ATTACK)
+            return fail(SDDC_ERR_ARG, "channel tone detector: attack %d outside 1..%d windows", attack, SDDC_DDC_TONE_MAX_ATTACK);
+        if (hang < 0 || hang > SDDC_DDC_TONE_MAX_HANG)
+            return fail(SDDC_ERR_ARG, "channel tone detector: hang %d outside 0..%d windows", hang, SDDC_DDC_TONE_MAX_HANG);
+        for (int fmt : {sense_format, in_format, out_format})
+            if (fmt != SDDC_DDC_AUDIO_F32 && fmt != SDDC_DDC_AUDIO_S16)
+                return fail(SDDC_ERR_ARG, "channel tone detector: unknown sample format %d", fmt);
+        try {
+            wd.assign(words, words + ntones);
+            mk.assign(masks, masks + nch);
+            thr.resize((size_t)nch * 3);
+        } catch (const std::exception &ex) {
+            return fail(SDDC_ERR_NOMEM, "channel tone detector: %s", ex.what());
+        }
+        for (int c = 0; c < nch; c++) {
+            const float ro = thresholds[3 * c], rc = thresholds[3 * c + 1], em = thresholds[3 * c + 2];
+            if (ntones < 64 && (masks[c] >> ntones) != 0)
+                return fail(SDDC_ERR_ARG, "channel tone detector: the mask of channel %d has a bit at or above ntones = %d", c, ntones);
+            if (!(ro > 0.f && ro <= 1.f) || !(rc > 0.f && rc <= 1.f))
+                return fail(SDDC_ERR_ARG, "channel tone detector: rho_open %g or rho_close %g of channel %d is outside (0, 1]",
+                            (double)ro, (double)rc, c);
+            if (!(rc <= ro))
+                return fail(SDDC_ERR_ARG, "channel tone detector: channel %d has rho_close %g above rho_open %g", c, (double)rc, (double)ro);
+            thr[3 * (size_t)c] = sddc::tone::tone_scale(ro, window);
+            thr[3 * (size_t)c + 1] = sddc::tone::tone_scale(rc, window);
+            thr[3 * (size_t)c + 2] = sddc::tone::tone_scale(em == 0.f ? 0.f : em, window);
+            if (!(em >= 0.f) || !std::isfinite(thr[3 * (size_t)c + 2]))
+                return fail(SDDC_ERR_ARG, "channel tone detector: e_min %g of channel %d is not a value >= 0 with a finite 256 W e_min",
+                            (double)em, c);
+        }
+    }
+    std::lock_guard<std::mutex> lk(h->mu);
+    ChannelTone &st = h->chtone;
+    if (h->cpu) {
+        st.clear();
+        if (off) return SDDC_OK;
+        try {
+            st.state_h.assign((size_t)nch, sddc::cpu::R2iq::ToneChannel());
+        } catch (const std::exception &ex) {
+            st.clear();
+            return fail(SDDC_ERR_NOMEM, "channel tone detector: %s", ex.what());
+        }
+    } else {
+        DeviceGuard g(h->device);
+        HIP_TRY(g.err);
+        HIP_TRY(st.readers.sync());   // earlier launches, on any stream, may still use the state
+        st.clear();                   // a failed upload leaves the stage off
+        if (off) return SDDC_OK;
+        const size_t nstate = (size_t)nch * sddc::kToneStateWords;
+        hipError_t e = hipMalloc(&st.d_tones, wd.size() * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMalloc(&st.d_masks, mk.size() * sizeof(uint64_t));
+        if (e == hipSuccess) e = hipMalloc(&st.d_thr, thr.size() * sizeof(float));
+        for (uint32_t *&p : st.d_state)
+            if (e == hipSuccess) e = hipMalloc(&p, nstate * sizeof(uint32_t));
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            st.clear();
+            return fail(SDDC_ERR_NOMEM, "channel tone detector: no device memory for %d channels", nch);
+        }
+        e = hipMemcpy(st.d_tones, wd.data(), wd.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(st.d_masks, mk.data(), mk.size() * sizeof(uint64_t), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(st.d_thr, thr.data(), thr.size() * sizeof(float), hipMemcpyHostToDevice);
+        // zeroed on the handle's stream and waited for: the first launch may be on any stream
+        for (uint32_t *p : st.d_state)
+            if (e == hipSuccess) e = hipMemsetAsync(p, 0, nstate * sizeof(uint32_t), h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) {
+            st.clear();
+            HIP_TRY(e);
+        }
+    }
+    st.words = std::move(wd);
+    st.max_mask_tones = 0;
+    for (uint64_t m : mk) st.max_mask_tones = std::max(st.max_mask_tones, __builtin_popcountll(m));
+    st.masks = std::move(mk);
+    st.thr = std::move(thr);
+    st.nch = nch;
+    st.ntones = ntones;
+    st.window = window;
+    st.attack = attack;
+    st.hang = hang;
+    st.sense_fmt = sense_format;
+    st.in_fmt = in_format;
+    st.out_fmt = out_format;
+    st.pos = 0;
+    return SDDC_OK;
+}
+
+int sddc_ddc_channel_tone_reset(sddc_ddc_t *h)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    ChannelTone &st = h->chtone;
+    if (st.masks.empty()) return fail(SDDC_ERR_STATE, "channel tone reset: no detector set");
+    if (h->cpu) {
+        std::fill(st.state_h.begin(), st.state_h.end(), sddc::cpu::R2iq::ToneChannel());
+    } else {
+        DeviceGuard g(h->device);
+        HIP_TRY(g.err);
+        HIP_TRY(st.readers.sync());   // earlier launches, on any stream, may still use the state
+        HIP_TRY(hipMemsetAsync(st.d_state[st.cur], 0, st.state_words() * sizeof(uint32_t), h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));   // the next launch may be on any stream
+    }
+    st.pos = 0;
+    return SDDC_OK;
+}
+
+int sddc_ddc_internal_chtone_set_position(sddc_ddc_t *h, uint64_t pos)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    ChannelTone &st = h->chtone;
+    if (st.masks.empty()) return fail(SDDC_ERR_STATE, "channel tone position: no detector set");
+    if (pos % ((uint64_t)SDDC_DDC_TONE_BLOCK * (uint64_t)st.window) != 0)
+        return fail(SDDC_ERR_ARG, "channel tone position: %llu is no multiple of 256 W = %d", (unsigned long long)pos,
+                    SDDC_DDC_TONE_BLOCK * st.window);
+    if (h->cpu) {
+        for (auto &ch : st.state_h) {
+            ch.E = 0.f;
+            ch.bad = 0;
+            std::fill(std::begin(ch.zr), std::end(ch.zr), 0.f);
+            std::fill(std::begin(ch.zi), std::end(ch.zi), 0.f);
+            std::fill(std::begin(ch.x), std::end(ch.x), 0.f);
+        }
+    } else {
+        DeviceGuard g(h->device);
+        HIP_TRY(g.err);
+        HIP_TRY(st.readers.sync());
+        // words 6 .. 135 of every channel: E, the bad flag, Zr and Zi (the stored block is not read at a block's start)
+        HIP_TRY(hipMemset2DAsync(st.d_state[st.cur] + 6, (size_t)sddc::kToneStateWords * 4, 0, (size_t)130 * 4, (size_t)st.nch,
+                                 h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+    st.pos = pos;
+    return SDDC_OK;
+}
+
+// the checks both calls share (under h->mu)
+static int check_chtone_args(const sddc_ddc_t *h, const void *sense, size_t sense_stride, const void *in, int nch, size_t nsamp,
+                             size_t in_stride, const void *out, size_t out_stride, const void *tone, const void *open,
+                             const void *count, const void *level, const void *powers)
+{
+    const ChannelTone &st = h->chtone;
+    if (st.masks.empty()) return fail(SDDC_ERR_STATE, "channel tone detector: no detector set");
+    if (nch != st.nch)
+        return fail(SDDC_ERR_STATE, "channel tone detector: the detector is set for %d channels, the call has %d", st.nch, nch);
+    if (nsamp == 0 || nsamp > ((size_t)1 << 40)) return fail(SDDC_ERR_ARG, "nsamp must be in 1..2^40 (got %zu)", nsamp);
+    if (!sense) return fail(SDDC_ERR_ARG, "null sense buffer");
+    if (nch > 1 && sense_stride < nsamp)
+        return fail(SDDC_ERR_ARG, "sense_stride must be >= nsamp (got %zu, nsamp %zu)", sense_stride, nsamp);
+    const uintptr_t ss = st.sense_fmt == SDDC_DDC_AUDIO_S16 ? 2 : 4;
+    if (((uintptr_t)sense & (ss - 1)) != 0) return fail(SDDC_ERR_ARG, "the sense buffer must be %d-byte aligned", (int)ss);
+    if ((((uintptr_t)tone | (uintptr_t)open | (uintptr_t)count | (uintptr_t)level | (uintptr_t)powers) & 3) != 0)
+        return fail(SDDC_ERR_ARG, "the side outputs must be 4-byte aligned");
+    if (!in && out) return fail(SDDC_ERR_ARG, "an output without audio");
+    if (in && !out) return fail(SDDC_ERR_ARG, "audio without an output");
+    if (!in) return SDDC_OK;
+    if (nch > 1 && in_stride < nsamp) return fail(SDDC_ERR_ARG, "in_stride must be >= nsamp (got %zu, nsamp %zu)", in_stride, nsamp);
+    if (nch > 1 && out_stride < nsamp)
+        return fail(SDDC_ERR_ARG, "out_stride must be >= nsamp (got %zu, nsamp %zu)", out_stride, nsamp);
+    const uintptr_t is = st.in_fmt == SDDC_DDC_AUDIO_S16 ? 2 : 4, os = st.out_fmt == SDDC_DDC_AUDIO_S16 ? 2 : 4;
+    if (((uintptr_t)in & (is - 1)) != 0) return fail(SDDC_ERR_ARG, "the input must be %d-byte aligned", (int)is);
+    if (((uintptr_t)out & (os - 1)) != 0) return fail(SDDC_ERR_ARG, "the output must be %d-byte aligned", (int)os);
+    const uintptr_t ia = (uintptr_t)in, oa = (uintptr_t)out, sa = (uintptr_t)sense;
+    const uintptr_t ib = ia + ((uintptr_t)(nch - 1) * (nch > 1 ? in_stride : 0) + nsamp) * is;
+    const uintptr_t ob = oa + ((uintptr_t)(nch - 1) * (nch > 1 ? out_stride : 0) + nsamp) * os;
+    const uintptr_t sb = sa + ((uintptr_t)(nch - 1) * (nch > 1 ? sense_stride : 0) + nsamp) * ss;
+    if (ia < ob && oa < ib) return fail(SDDC_ERR_ARG, "the input and the output overlap");
+    if (sa < ob && oa < sb) return fail(SDDC_ERR_ARG, "the sense buffer and the output overlap");
+    return SDDC_OK;
+}
+
+// The call in launch sets of at most run_blocks blocks per channel, rounded down to whole windows (the
+// scratch holds four words per channel and window of a set, and the kernels index a set with an int).
+static int chtone_launch(sddc_ddc_t *h, const void *d_sense, size_t sense_stride, const void *d_in, int nch, size_t nsamp,
+                         size_t in_stride, void *d_out, size_t out_stride, int32_t *d_tone, uint32_t *d_open, uint32_t *d_count,
+                         float *d_level, float *d_powers, hipStream_t s)
+{
+    ChannelTone &st = h->chtone;
+    const size_t B = SDDC_DDC_TONE_BLOCK, W = (size_t)st.window, WB = W * B;
+    const size_t run_blocks = (size_t)(st.run_blocks > 0 ? st.run_blocks : ChannelTone::kDefaultRunBlocks);
+    const size_t run_windows = run_blocks / W > 0 ? run_blocks / W : 1;
+    const size_t hs0 = (size_t)(st.pos % WB), windows = (hs0 + nsamp + WB - 1) / WB;
+    const size_t need = (size_t)nch * (windows < run_windows ? windows : run_windows) * 4;
+    if (need > st.scratch_cap) {
+        HIP_TRY(st.readers.sync());   // an earlier launch may still use the scratch
+        if (int rc = grow_device_buffer(&st.d_scratch, &st.scratch_cap, need, "channel tone detector", "scratch words")) return rc;
+    }
+    HIP_TRY(st.readers.order_before(s));
+    const bool s16 = st.sense_fmt == SDDC_DDC_AUDIO_S16, in16 = st.in_fmt == SDDC_DDC_AUDIO_S16, out16 = st.out_fmt == SDDC_DDC_AUDIO_S16;
+    const size_t ss = s16 ? 2 : 4, is = in16 ? 2 : 4, os = out16 ? 2 : 4;
+    hipError_t e = hipSuccess;
+    for (size_t done = 0; done < nsamp && e == hipSuccess;) {
+        const size_t hs = (size_t)(st.pos % WB);
+        size_t n = nsamp - done;
+        if (n > run_windows * WB - hs) n = run_windows * WB - hs;
+        e = sddc::launch_channel_tone(h->tables, static_cast<const char *>(d_sense) + done * ss, s16, sense_stride,
+                                      d_in ? static_cast<const char *>(d_in) + done * is : nullptr, in16, nch, n, in_stride, st.pos,
+                                      st.d_tones, st.ntones, st.d_masks, st.max_mask_tones, st.d_thr, st.window, st.attack, st.hang, st.d_state[st.cur],
+                                      st.d_state[st.cur ^ 1], st.d_scratch, d_in ? static_cast<char *>(d_out) + done * os : nullptr,
+                                      out16, out_stride, d_tone, d_open, d_count, d_level, d_powers, done > 0, st.max_wgs, h->device, s);
+        if (e != hipSuccess) break;
+        st.cur ^= 1;
+        st.pos += n;
+        done += n;
+    }
+    const hipError_t er = st.readers.record(s);   // whatever was enqueued stays ordered
+    HIP_TRY(e);
+    HIP_TRY(er);
+    return SDDC_OK;
+}
+
+int sddc_ddc_channel_tone_device(sddc_ddc_t *h, const void *d_sense, size_t sense_stride, const void *d_audio, int nch,
+                                 size_t nsamp, size_t in_stride, void *d_out, size_t out_stride, int32_t *d_tone,
+                                 uint32_t *d_open, uint32_t *d_count, float *d_level, float *d_powers, void *hip_stream)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->cpu) return fail(SDDC_ERR_STATE, "channel_tone_device: a CPU handle has no device path");
+    if (int rc = check_chtone_args(h, d_sense, sense_stride, d_audio, nch, nsamp, in_stride, d_out, out_stride, d_tone, d_open, d_count,
+                                   d_level, d_powers))
+        return rc;
+    DeviceGuard g(h->device);
+    HIP_TRY(g.err);
+    return chtone_launch(h, d_sense, sense_stride, d_audio, nch, nsamp, in_stride, d_out, out_stride, d_tone, d_open, d_count, d_level,
+                         d_powers, (hipStream_t)hip_stream);
+}
+
+int sddc_ddc_channel_tone_host(sddc_ddc_t *h, const void *sense, size_t sense_stride, const void *audio, int nch, size_t nsamp,
+                               size_t in_stride, void *out, size_t out_stride, int32_t *tone, uint32_t *open, uint32_t *count,
+                               float *level, float *powers)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (int rc = check_chtone_args(h, sense, sense_stride, audio, nch, nsamp, in_stride, out, out_stride, tone, open, count, level, powers))
+        return rc;
+    ChannelTone &st = h->chtone;
+    const bool s16 = st.sense_fmt == SDDC_DDC_AUDIO_S16, in16 = st.in_fmt == SDDC_DDC_AUDIO_S16, out16 = st.out_fmt == SDDC_DDC_AUDIO_S16;
+    if (h->cpu) {
+        sddc::cpu::R2iq::channel_tone(sense, s16, audio, in16, nch, nsamp, nch > 1 ? sense_stride : 0, nch > 1 ? in_stride : 0,
+                                      st.words.data(), st.ntones, st.masks.data(), st.thr.data(), st.window, st.attack, st.hang, st.pos,
+                                      st.state_h.data(), out, out16, nch > 1 ? out_stride : 0, tone, open, count, level, powers);
+        st.pos += nsamp;
+        return SDDC_OK;
+    }
+    DeviceGuard g(h->device);
+    HIP_TRY(g.err);
+    // the spans that hold every channel's samples and outputs
+    const size_t ss = s16 ? 2 : 4, is = in16 ? 2 : 4, os = out16 ? 2 : 4;
+    const size_t sense_bytes = ((size_t)(nch - 1) * (nch > 1 ? sense_stride : 0) + nsamp) * ss;
+    const size_t in_bytes = audio ? ((size_t)(nch - 1) * (nch > 1 ? in_stride : 0) + nsamp) * is : 0;
+    const size_t out_bytes = audio ? ((size_t)(nch - 1) * (nch > 1 ? out_stride : 0) + nsamp) * os : 0;
+    const size_t n = (size_t)nch;
+    if (int rc = grow_device_buffer(&st.d_sense, &st.sense_cap, sense_bytes, "channel_tone_host", "sense bytes")) return rc;
+    if (audio) {
+        if (int rc = grow_device_buffer(&st.d_in, &st.in_cap, in_bytes, "channel_tone_host", "input bytes")) return rc;
+        if (int rc = grow_device_buffer(&st.d_out, &st.out_cap, out_bytes, "channel_tone_host", "output bytes")) return rc;
+    }
+    if (int rc = grow_device_buffer(&st.d_side, &st.side_cap, n * (5 + (size_t)st.ntones), "channel_tone_host", "side outputs")) return rc;
+    int32_t *d_tone = tone ? reinterpret_cast<int32_t *>(st.d_side) : nullptr;
+    uint32_t *d_open = open ? st.d_side + n : nullptr, *d_count = count ? st.d_side + 2 * n : nullptr;
+    float *d_level = level ? reinterpret_cast<float *>(st.d_side + 3 * n) : nullptr;
+    float *d_powers = powers ? reinterpret_cast<float *>(st.d_side + 5 * n) : nullptr;
+    HIP_TRY(hipMemcpyAsync(st.d_sense, sense, sense_bytes, hipMemcpyHostToDevice, h->stream));
+    if (audio) HIP_TRY(hipMemcpyAsync(st.d_in, audio, in_bytes, hipMemcpyHostToDevice, h->stream));
+    const int rc = chtone_launch(h, st.d_sense, sense_stride, audio ? st.d_in : nullptr, nch, nsamp, in_stride, audio ? st.d_out : nullptr,
+                                 out_stride, d_tone, d_open, d_count, d_level, d_powers, h->stream);
+    if (rc == SDDC_OK) {   // the streams alone: the caller's memory between them stays as it is
+        if (audio) {
+            if (nch == 1 || out_stride == nsamp)
+                HIP_TRY(hipMemcpyAsync(out, st.d_out, out_bytes, hipMemcpyDeviceToHost, h->stream));
+            else
+                HIP_TRY(hipMemcpy2DAsync(out, out_stride * os, st.d_out, out_stride * os, nsamp * os, n, hipMemcpyDeviceToHost,
+                                         h->stream));
+        }
+        if (tone) HIP_TRY(hipMemcpyAsync(tone, d_tone, n * 4, hipMemcpyDeviceToHost, h->stream));
+        if (open) HIP_TRY(hipMemcpyAsync(open, d_open, n * 4, hipMemcpyDeviceToHost, h->stream));
+        if (count) HIP_TRY(hipMemcpyAsync(count, d_count, n * 4, hipMemcpyDeviceToHost, h->stream));
+        if (level) HIP_TRY(hipMemcpyAsync(level, d_level, n * 8, hipMemcpyDeviceToHost, h->stream));
+        if (powers) HIP_TRY(hipMemcpyAsync(powers, d_powers, n * (size_t)st.ntones * 4, hipMemcpyDeviceToHost, h->stream));
     }
     HIP_TRY(hipStreamSynchronize(h->stream));   // also after a failed launch: the caller's input is free again
     return rc;

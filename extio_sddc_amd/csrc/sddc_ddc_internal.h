@@ -115,7 +115,22 @@ extern "C" {
  * length changes no output bit and no side output (tests). */
 #define SDDC_DDC_PARAM_CHSQ_RUN_BLOCKS 24
 
+/* SDDC_DDC_PARAM_CHTONE_MAX_WGS = n > 0: each of the channel tone detector's grids is at most n workgroups,
+ * as param 23 for the squelch; 0 (default): full residency with a loop.  The grid changes no output bit and
+ * no side output (tests). */
+#define SDDC_DDC_PARAM_CHTONE_MAX_WGS 25
+
+/* SDDC_DDC_PARAM_CHTONE_RUN_BLOCKS = n in 1..2^20: a call of the channel tone detector is cut into launch
+ * sets of at most n blocks per channel, rounded down to whole windows (at least one); 0: 4096.  The run
+ * length changes no output bit and no side output (tests). */
+#define SDDC_DDC_PARAM_CHTONE_RUN_BLOCKS 26
+
 int sddc_ddc_internal_set_param(sddc_ddc_t *h, int param, int value);
+/* Move the channel tone detector's stream position to pos, a multiple of 256 W (SDDC_ERR_ARG otherwise;
+ * SDDC_ERR_STATE: no detector set): the unfinished window's sums and the unfinished block are cleared, the
+ * gate and the last window's results are kept.  It lets tests start a stream next to the 2^32 wrap of the
+ * sample phase. */
+int sddc_ddc_internal_chtone_set_position(sddc_ddc_t *h, uint64_t pos);
 /* A given table of n relative shares (n = the d = 0 kernel's full-residency grid, 4 x CUs) used as
  * it is, without clamps or measurements, until n = 0 clears it (tests). */
 int sddc_ddc_internal_fs_set_shares(sddc_ddc_t *h, const float *shares, int n);

@@ -194,6 +194,26 @@ def squelch_blocks(seconds: float, fs: float) -> int:
     return int(b.value)
 
 
+TONE_BLOCK = 256                          # SDDC_DDC_TONE_BLOCK: the tone detector's block length B
+# the 50 standard CTCSS frequencies in Hz
+CTCSS_TONES = (67.0, 69.3, 71.9, 74.4, 77.0, 79.7, 82.5, 85.4, 88.5, 91.5, 94.8, 97.4, 100.0, 103.5, 107.2, 110.9, 114.8,
+               118.8, 123.0, 127.3, 131.8, 136.5, 141.3, 146.2, 151.4, 156.7, 159.8, 162.2, 165.5, 167.9, 171.3, 173.8,
+               177.3, 179.9, 183.5, 186.2, 189.9, 192.8, 196.6, 199.5, 203.5, 206.5, 210.7, 218.1, 225.7, 229.1, 233.6,
+               241.8, 250.3, 254.1)
+
+
+def tone_word(f: float, fs: float) -> int:
+    """The phase word of a tone of f Hz at the sample rate fs: round(f / fs * 2^32) mod 2^32 (sddc_ddc_bfo_word)."""
+    return bfo_word(float(f) / float(fs))
+
+
+def tone_window(seconds: float, fs: float) -> int:
+    """A window of `seconds` at the rate fs in blocks of 256 samples, rounded, 1..256 (sddc_ddc_tone_window)."""
+    b = ctypes.c_int()
+    check(_lib.load().sddc_ddc_tone_window(float(seconds), float(fs), ctypes.addressof(b)))
+    return int(b.value)
+
+
 def psd_to_dbfs(psd) -> np.ndarray:
     """R2iq.spectrum's output in dB relative to a full-scale real tone (amplitude 32768 reads
     32768^2 / 4 at its bin centre): 10 log10(4 psd / 32768^2); -inf where psd is 0."""
@@ -227,6 +247,7 @@ class R2iq:
         self._agc = None     # (nch, in_format, out_format) of setChannelAgc
         self._blanker = None  # (nch, format) of setChannelBlanker
         self._squelch = None  # (nch, sense, in_format, out_format) of setChannelSquelch
+        self._tone = None     # (nch, ntones, sense_format, in_format, out_format) of setChannelToneDetector
 
     # -- lifecycle --------------------------------------------------------
     @property
@@ -1025,6 +1046,112 @@ class R2iq:
                                                       nch, nsamp, in_stride, sense_stride, d_out.data_ptr(), out_stride,
                                                       *(None if t is None else t.data_ptr() for _, t, _ in sides),
                                                       _stream_handle(stream)))
+
+    # -- channel tone detector ----------------------------------------------------
+    def setChannelToneDetector(self, words, masks, thresholds, window: int = 16, attack: int = 1, hang: int = 0,
+                               fmt_sense: int = AUDIO_F32, fmt_in: int = AUDIO_F32, fmt_out: int = AUDIO_F32) -> None:
+        """The streaming tone squelch of channel_tone: words is uint32 [ntones], 1..64 phase words (tone_word);
+        masks uint64 [nch], the tones each channel listens for (0: bypass, always open); thresholds float32
+        [nch, 3] = (rho_open, rho_close, e_min): the share of a window's energy in its best tone that opens and
+        that keeps open (0 < rho_close <= rho_open <= 1) and the mean square per sample below which a window is
+        silence.  window: 1..256 blocks of 256 samples (tone_window); attack: 1..255 windows before a channel
+        opens; hang: 0..65535 windows it stays open without the tone; fmt_*: AUDIO_F32 or AUDIO_S16 of the
+        sense stream, the audio and the output.  Every call zeroes the state and the stream position.
+        words=None turns the stage off."""
+        if words is None or np.size(words) == 0:
+            check(self._L.sddc_ddc_set_channel_tone_detector(self._h, None, 0, None, None, 0, 0, 0, 0, 0, 0, 0))
+            self._tone = None
+            return
+        w = np.ascontiguousarray(np.asarray(words, np.uint32).reshape(-1))
+        m = np.ascontiguousarray(np.asarray(masks, np.uint64).reshape(-1))
+        t = np.ascontiguousarray(np.asarray(thresholds, np.float32))
+        if t.ndim != 2 or t.shape != (m.shape[0], 3):
+            raise DDCError(-1, "thresholds must be [nch, 3] with one row per mask")
+        check(self._L.sddc_ddc_set_channel_tone_detector(self._h, w.ctypes.data, w.shape[0], m.ctypes.data, t.ctypes.data,
+                                                         m.shape[0], int(window), int(attack), int(hang), int(fmt_sense),
+                                                         int(fmt_in), int(fmt_out)))
+        self._tone = (m.shape[0], w.shape[0], int(fmt_sense), int(fmt_in), int(fmt_out))
+
+    def resetChannelToneDetector(self) -> None:
+        """Zero every channel's state and the stream position: the next call starts a closed stream."""
+        check(self._L.sddc_ddc_channel_tone_reset(self._h))
+
+    def channel_tone(self, sense: np.ndarray, audio=None):
+        """The tone detector on host arrays: sense is float32 (AUDIO_S16 sense: int16) [nch, nsamp], any nsamp
+        >= 1; audio None (detect only) or float32 / int16 [nch, nsamp]; a single stream may drop the channel
+        axis.  Returns a dict: out (float32 / int16 [nch, nsamp], None without audio), tone (int32 [nch], the
+        best tone of the last completed window where it held the closing threshold, else -1), open (uint32
+        [nch]), count (uint32 [nch], this call's samples in open windows), level (float32 [nch, 2] = P_best, E
+        of the last completed window), powers (float32 [nch, ntones]).  Keeps every channel's state for the
+        next call."""
+        if self._tone is None:
+            raise DDCError(-4, "no channel tone detector set")
+        nch, ntones, fs, fin, fout = self._tone
+        s = np.asarray(sense, np.int16 if fs == AUDIO_S16 else np.float32)
+        if s.ndim == 1:
+            s = s[None, :]
+        s = np.ascontiguousarray(s)
+        if s.ndim != 2 or s.shape[1] < 1:
+            raise DDCError(-1, "sense must be [nch, nsamp] with nsamp >= 1")
+        n, nsamp = s.shape
+        a = out = None
+        if audio is not None:
+            a = np.asarray(audio, np.int16 if fin == AUDIO_S16 else np.float32)
+            if a.ndim == 1:
+                a = a[None, :]
+            a = np.ascontiguousarray(a)
+            if a.shape != s.shape:
+                raise DDCError(-1, "the audio must have the sense stream's [nch, nsamp]")
+            out = np.empty((n, nsamp), np.int16 if fout == AUDIO_S16 else np.float32)
+        tone = np.empty(n, np.int32)
+        o = np.empty(n, np.uint32)
+        c = np.empty(n, np.uint32)
+        lv = np.empty((n, 2), np.float32)
+        pw = np.empty((n, ntones), np.float32)
+        check(self._L.sddc_ddc_channel_tone_host(self._h, s.ctypes.data, nsamp, None if a is None else a.ctypes.data, n, nsamp,
+                                                 nsamp, None if out is None else out.ctypes.data, nsamp, tone.ctypes.data,
+                                                 o.ctypes.data, c.ctypes.data, lv.ctypes.data, pw.ctypes.data))
+        return {"out": out, "tone": tone, "open": o, "count": c, "level": lv, "powers": pw}
+
+    def channel_tone_device(self, d_sense, sense_stride: int, d_audio, nch: int, nsamp: int, in_stride: int, d_out,
+                            out_stride: int, d_tone=None, d_open=None, d_count=None, d_level=None, d_powers=None,
+                            stream=None) -> None:
+        """The tone detector on device buffers: d_sense is a float32 (AUDIO_S16 sense: int16) device tensor,
+        channel c's nsamp samples at c * sense_stride; d_audio None (detect only, d_out None too) or the audio
+        buffer of the demodulator, the audio filter or the AGC, channel c's samples at c * in_stride, with d_out
+        its gated copy at c * out_stride; d_out must overlap neither input.  d_tone, d_open, d_count: None or
+        int32 device tensors of nch values; d_level: None or float32 [nch, 2]; d_powers: None or float32 [nch,
+        ntones].  Enqueued on `stream` like process_device; the calls of one handle run in call order."""
+        import torch
+        if self._tone is None:
+            raise DDCError(-4, "no channel tone detector set")
+        _, ntones, fs, fin, fout = self._tone
+        if nch < 1 or nsamp < 1:
+            raise DDCError(-1, "nch and nsamp must be >= 1")
+        if (d_audio is None) != (d_out is None):
+            raise DDCError(-1, "d_audio and d_out go together")
+        sides = (("d_tone", d_tone, torch.int32, nch), ("d_open", d_open, torch.int32, nch), ("d_count", d_count, torch.int32, nch),
+                 ("d_level", d_level, torch.float32, 2 * nch), ("d_powers", d_powers, torch.float32, nch * ntones))
+        if not all(t is None or t.is_cuda for t in (d_sense, d_audio, d_out, d_tone, d_open, d_count, d_level, d_powers)):
+            raise DDCError(-1, "device path needs device tensors")
+        bufs = [("d_sense", d_sense, sense_stride, torch.int16 if fs == AUDIO_S16 else torch.float32)]
+        if d_audio is not None:
+            bufs += [("d_audio", d_audio, in_stride, torch.int16 if fin == AUDIO_S16 else torch.float32),
+                     ("d_out", d_out, out_stride, torch.int16 if fout == AUDIO_S16 else torch.float32)]
+        for name, t, stride, dt in bufs:
+            if t is None or t.dtype != dt or not t.is_contiguous():
+                raise DDCError(-1, f"{name} must be a contiguous {dt} tensor")
+            need = (nch - 1) * stride + nsamp
+            if t.numel() < need:
+                raise DDCError(-1, f"{name} has {t.numel()} samples, need {need}")
+        for name, t, dt, cnt in sides:
+            if t is not None and (t.dtype != dt or not t.is_contiguous() or t.numel() < cnt):
+                raise DDCError(-1, f"{name} must be a contiguous {dt} tensor of at least {cnt} values")
+        check(self._L.sddc_ddc_channel_tone_device(self._h, d_sense.data_ptr(), sense_stride,
+                                                   None if d_audio is None else d_audio.data_ptr(), nch, nsamp, in_stride,
+                                                   None if d_out is None else d_out.data_ptr(), out_stride,
+                                                   *(None if t is None else t.data_ptr() for _, t, _, _ in sides),
+                                                   _stream_handle(stream)))
 
 
 def _check_device_buffers(d_in, nblk, d_out, out_floats, fmt=0):

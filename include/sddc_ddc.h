@@ -753,7 +753,7 @@ int sddc_ddc_channel_blank_host(sddc_ddc_t *h, const void *iq, int nch, size_t n
  * = the demodulator's IQ input, LEVEL), an FM noise squelch (sense = the discriminator audio through a
  * high-pass of the audio filter into a second buffer, NOISE) and a plain audio-level gate (SELF).  What
  * this squelch is NOT: it has no look-ahead (up to A + 1 blocks of a transmission's start are lost), no
- * tone (CTCSS) decode, and its thresholds do not adapt to the noise floor.
+ * tone (CTCSS) decode (that is the channel tone detector below), and its thresholds do not adapt to the noise floor.
  *
  * The definition (normative; csrc/squelch_math.h holds the operations, shared by both backends, float,
  * contraction off, only *, +, comparisons, selects and integers).  B = SDDC_DDC_SQUELCH_BLOCK = 256; i >= 0
@@ -843,6 +843,95 @@ int sddc_ddc_channel_squelch_device(sddc_ddc_t *h, const void *d_audio, const vo
 int sddc_ddc_channel_squelch_host(sddc_ddc_t *h, const void *audio, const void *sense, int nch, size_t nsamp,
                                   size_t in_stride, size_t sense_stride, void *out, size_t out_stride, uint32_t *open,
                                   uint32_t *count, float *level);
+
+/* ---- channel tone detector: streaming per-channel CTCSS / tone squelch ---------------------------
+ * The squelch opens on level alone.  Where a frequency is shared, a transmission is told from the others
+ * by its sub-audible tone (CTCSS); a scanner wants to know which tone a transmission carries; a 1750 Hz
+ * burst, a paging tone or a DTMF pair are the same question.  This stage is a bank of single-bin DFTs
+ * (Goertzel filters) per channel over a real sense stream, a gate on the channel's audio that opens when
+ * the strongest tone of the channel's mask holds enough of the window's energy, and side outputs that name
+ * the tone and give every tone's power.  What it is NOT: no DCS (a digital code), no look-ahead (the gate of
+ * a window comes from the windows before it), and the window length bounds the decode time.
+ *
+ * The definition (normative; csrc/tone_math.h holds the operations, shared by both backends, float,
+ * contraction off, only *, +, explicit fmaf, comparisons, selects and integers).  B = SDDC_DDC_TONE_BLOCK =
+ * 256; p >= 0 is the stream index since the last set or reset, k = p div B its block, j = k div W its window.
+ *   Per handle.  A tone table of ntones (1..64) phase words w_t in 2^-32 cycles per sample (sddc_ddc_bfo_word
+ *                makes them); a window of W blocks (1..256); an attack of A windows (1..255); a hang of H
+ *                windows (0..65535); the formats of the sense stream, the audio and the output.
+ *   Per channel. A 64-bit tone mask (a bit at or above ntones is an argument error; 0 is bypass: always
+ *                open, the audio passes, the tone is -1) and three thresholds: rho_open >= rho_close, both in
+ *                (0, 1], the share of the window's energy in the best tone, and e_min >= 0, a mean square per
+ *                sample below which a window counts as silence.  Scaled once at set time: To = (float)((double)
+ *                rho_open * 256 W), Tc likewise, Emin = (float)((double)e_min * 256 W).
+ *   Sense.       Real, SDDC_DDC_AUDIO_F32 or _S16 (read as (float)v).  q = x * x; a sample with !(q <= FLT_MAX)
+ *                enters every sum as x = 0, q = 0 and marks its window bad.
+ *   Block k.     For each tone t of the mask: (c_i, s_i) = sincos_word(w_t * i) (the demodulator's
+ *                demod_sincos_word; the product as a uint32; i = 0..255); a_i = x_i * c_i, b_i = x_i * s_i; Ck,
+ *                Sk = the balanced pairwise tree (the blanker's) over a and over b; (cr, sr) = sincos_word(w_t *
+ *                (uint32)(256 k)); Re_k = fmaf(Ck, cr, -(Sk * sr)), Im_k = fmaf(Ck, sr, Sk * cr).  p_k = the
+ *                tree over q.
+ *   Window j.    Zr, Zi, E = the left folds from +0, in block order, of Re_k, Im_k, p_k.  P_t = (Zr * Zr) + (Zi
+ *                * Zi).  The best tone: the ascending scan of the mask, replaced only on a strict >.  u = !bad &&
+ *                E > Emin && P_best > To * E; v the same with Tc.
+ *   Gate.        The squelch's state machine, once per completed window: r = u ? min(r + 1, A) : 0; n = v ? 0 :
+ *                min(n + 1, H + 1); open = open ? (n <= H) : (r >= A); all zero on a new stream.  The gate
+ *                after window j applies to window j + 1.
+ *   Audio.       Optional (d_audio NULL: detect only), F32 or S16 in and out.  A sample of an open window
+ *                passes bit for bit (a NaN payload survives F32 to F32; S16 to F32 is (float)v, F32 to S16 the
+ *                demodulator's conversion); a closed one is +0.
+ *   Side outputs, each NULL or nch entries: tone (int32): the best tone of the last completed window if v
+ *                held there, else -1; open (uint32): the gate after the last completed window (bypass: 1);
+ *                count (uint32, modulo 2^32): the call's samples in open windows, consecutive calls add up;
+ *                level ([nch][2] float): P_best and E of the last completed window, the figures to calibrate
+ *                rho (P_best / (256 W E)) and e_min (E / (256 W)) from; powers ([nch][ntones] float): every
+ *                P_t of the last completed window, 0 for tones outside the mask (a scanner's or a DTMF
+ *                decoder's input).  Before any window completes: -1, 0 (bypass: 1), zeros.
+ * Outputs and side outputs are bit-identical from run to run, for any grid, run length and cut of a
+ * stream into calls, for a channel alone or among others, and between a GPU handle and a CPU handle, for
+ * samples that are 0 or of magnitude in [2^-40, 2^40] (tone_math.h shows why nothing that decides
+ * overflows or is subnormal there).  Against a float64 evaluation of the same definition, with X the sum
+ * of |x| over the window, eps = (38 + W) 2^-24 and u = 2^-24: |P_t - P_t64| <= 1.01 (2 sqrt(2) eps X sqrt(P64) +
+ * 2 eps^2 X^2 + 3 u P64) and |To E - (To E)64| <= 1.01 (W + 9) u To E64 (derived in tone_math.h).
+ * State per handle, on the device for a GPU handle, independent of every other stage's: the position; per
+ * channel the gate, the last completed window's results, the unfinished window's sums and bad flag, and
+ * the unfinished block's samples. */
+#define SDDC_DDC_TONE_BLOCK 256
+#define SDDC_DDC_TONE_MAX_TONES 64
+#define SDDC_DDC_TONE_MAX_WINDOW 256
+#define SDDC_DDC_TONE_MAX_ATTACK 255
+#define SDDC_DDC_TONE_MAX_HANG 65535
+/* blocks = round(seconds * fs / 256), at least 1: a window in blocks.  SDDC_ERR_ARG if the result is above
+ * 256, an argument is not finite, seconds < 0, fs <= 0 or blocks is NULL.  Stateless. */
+int sddc_ddc_tone_window(double seconds, double fs, int *blocks);
+/* words: host array [ntones]; masks: host array [nch]; thresholds: host array [nch][3] = (rho_open,
+ * rho_close, e_min); 1 <= nch <= SDDC_DDC_MAX_CHANNELS; window, attack, hang in blocks / windows as above;
+ * the formats SDDC_DDC_AUDIO_F32 or _S16.  A violation returns SDDC_ERR_ARG and sets nothing.  words, masks
+ * or thresholds NULL or nch == 0 turns the stage off and frees its state.  Every set call zeroes the state
+ * and the position, and waits for the stage's launches in flight. */
+int sddc_ddc_set_channel_tone_detector(sddc_ddc_t *h, const uint32_t *words, int ntones, const uint64_t *masks,
+                                       const float *thresholds, int nch, int window, int attack, int hang, int sense_format,
+                                       int in_format, int out_format);
+/* zero the state and the position: the next call starts a closed stream (SDDC_ERR_STATE: no detector set) */
+int sddc_ddc_channel_tone_reset(sddc_ddc_t *h);
+/* GPU handles; enqueued on hip_stream, returns after launch.  Channel c's nsamp sense samples at d_sense +
+ * c * sense_stride samples; with d_audio not NULL its audio at d_audio + c * in_stride and its outputs at
+ * d_out + c * out_stride; strides >= nsamp for nch > 1; bases aligned to a sample; any 1 <= nsamp <= 2^40.
+ * The output must overlap neither input; nothing is written between the streams or outside them.  d_tone,
+ * d_open, d_count: NULL or nch device entries; d_level: NULL or [nch][2]; d_powers: NULL or [nch][ntones].
+ * SDDC_ERR_STATE: no detector set, another nch than the set one, a CPU handle.  SDDC_ERR_ARG: the rest
+ * (d_out without d_audio and d_audio without d_out among them).  A failed call changes no state.  The calls
+ * of one handle share the state and the position: they run one after the other in call order, whatever
+ * their streams. */
+int sddc_ddc_channel_tone_device(sddc_ddc_t *h, const void *d_sense, size_t sense_stride, const void *d_audio, int nch,
+                                 size_t nsamp, size_t in_stride, void *d_out, size_t out_stride, int32_t *d_tone,
+                                 uint32_t *d_open, uint32_t *d_count, float *d_level, float *d_powers, void *hip_stream);
+/* Host buffers, the same layouts.  GPU handle: copy in, kernels, copy back, synchronous; it advances the
+ * same device state as the device call.  CPU handle: the definition's loop through the same arithmetic
+ * header. */
+int sddc_ddc_channel_tone_host(sddc_ddc_t *h, const void *sense, size_t sense_stride, const void *audio, int nch, size_t nsamp,
+                               size_t in_stride, void *out, size_t out_stride, int32_t *tone, uint32_t *open, uint32_t *count,
+                               float *level, float *powers);
 
 /* ---- ingest ---------------------------------------
  * Pin a caller-owned host region (hipHostRegister) so the host path DMAs blocks
