@@ -41,6 +41,10 @@
 // wave-frame and 128 -> 120 VGPRs in the benchmark instance, about 2 us of a 201 us launch
 // (profiles/packed_bases).  Fusing wave 0's mirror selects into the DPP read (149 ->
 // 122 VALU in its split) measured neutral with and without the packed bases and is not here.
+// The registers the packed bases freed hold the split's P: the static plain instances with four or
+// more zero rows (the benchmark's among them, at 126 VGPRs) read no table in the frame loop, the
+// one with three a single pair (fs_cached_pairs; 2.8-3.7 us of a 200 us launch,
+// profiles/cached_p_pairs).
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -156,6 +160,25 @@ constexpr int kQWave = 3;
 // holding forward pass 2's eight product twiddle powers in registers across frames (26 VALU per
 // wave-frame fewer, 128 VGPRs, spills in the NCO / CS16 instances) measured neutral (same files).
 constexpr int kFsPqAhead = 1;
+// The bin pairs (p, 15 - p), p below the count, whose P the static plain instance of ZR holds in
+// registers for the whole launch (cp[] in r2iq_fs_kernel): the most that leave the instance at
+// 128 VGPRs or fewer without scratch, i.e. at four workgroups per CU.
+//   |ZR|      pairs held                        VGPRs (before)   P loads left per frame
+//   0, 2      none                              117              every pair
+//   3         7: 3 single-bin + 4 full pairs    126 (116-117)    1 (pair 7; all 8: 8 bytes of scratch)
+//   4         8: 4 single-bin + 4 full pairs    126 (118-120)    none
+//   5         8: 5 + 3                          123 (116)        none
+//   6         8: 6 + 2                          120 (117)        none
+//   7, 8      8: every live row (as before)     117, 114         none
+// (profiles/cached_p_pairs/resources.txt).  The comparison library (-DSDDC_FS_RECOMPUTED=1) keeps
+// the earlier counts, |ZR| at 3 and 8 and |ZR| + 1 between, and so the per-frame loads of the rest.
+constexpr int fs_cached_pairs(int zr)
+{
+    const int a = zr > 0 ? zr : -zr;
+    if (a < 3) return 0;
+    if (SDDC_FS_RECOMPUTED) return a >= 4 && a <= 7 ? a + 1 : a;
+    return a == 3 ? 7 : 8;
+}
 // fs_row_slot, fs_pair_row / _col / _slot, fs_col_slot, fs_tw_slot: fs_bases.h
 // The exchanges' LDS layout (round 6): row R (0..255), column j (0..15) at
 //   fs_slot(R, j) = 272 (R >> 4) + [R >= 128] + 34 ((R & 15) >> 1) + (R & 1) + 2 j:
@@ -288,7 +311,7 @@ __global__ __launch_bounds__(NT, 4) void r2iq_fs_kernel(
     // drops to 8 bytes per bin) and, for the static schedule, I2's lane factors g_t, g_t W^{-t},
     // g_t W^{-4t} (6 VGPRs; the queue and stealing schedules, at 124-128 VGPRs, keep the loads).
     // Per frame 12 KB of table reads fewer at tb = 1024: +2.5-3 % (profiles/r06/ab/
-    // fs_cached_r_and_lane_factors_*.txt).  118 VGPRs at ZR = 4 (128 with the P pairs below).
+    // fs_cached_r_and_lane_factors_*.txt).
     float cr[16];
     {
         const __amdgpu_buffer_rsrc_t rr = buf_rsrc(reinterpret_cast<const float *>(pqf) + 2 * HALF);
@@ -296,13 +319,13 @@ __global__ __launch_bounds__(NT, 4) void r2iq_fs_kernel(
         for (int k = 0; k < 16; k++)
             if (!zrow<ZR>(k)) cr[k] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rr, 4u * tid, 4u * NT * k, 0));
     }
-    // The plain static instances with zero rows (108-120 VGPRs before) also hold P of their first
-    // pairs p, 15 - p in registers: the |ZR| single-bin pairs (one row zero) and, at |ZR| = 4..7,
-    // one two-bin pair (at |ZR| = 7, 8 every live row; 122-126 VGPRs).  At tb 1024 (|ZR| = 4)
-    // 6 of 12 P loads per lane and frame stay: +1.4 %; |ZR| = 5..8: +1.2-2.7 %, bit-identical
-    // (profiles/r06/ab/fs_cached_p_*.txt)
-    constexpr int AZR = ZR > 0 ? ZR : -ZR;
-    constexpr int CPP = SCHED == kSchedStatic && !NCO && !CS16 && AZR >= 3 ? (AZR >= 4 && AZR <= 7 ? AZR + 1 : AZR) : 0;
+    // The plain static instances with three or more zero rows also hold P of their first pairs
+    // p, 15 - p in registers (fs_cached_pairs: at |ZR| >= 4 every live row, at |ZR| = 3 all but
+    // pair 7).  The |ZR| single-bin pairs and one two-bin pair: +1.4 % at tb 1024, +1.2-2.7 % at
+    // |ZR| = 5..8 (profiles/r06/ab/fs_cached_p_*.txt); the remaining three pairs at tb 1024, 12 KB
+    // of L2 reads per frame and the loop's last table loads: +1.4-1.9 %, bit-identical
+    // (profiles/cached_p_pairs).
+    constexpr int CPP = SCHED == kSchedStatic && !NCO && !CS16 ? fs_cached_pairs(ZR) : 0;
     float2 cp[16];
     if constexpr (CPP > 0) {
         const __amdgpu_buffer_rsrc_t rq = buf_rsrc(pqf);
@@ -333,6 +356,12 @@ __global__ __launch_bounds__(NT, 4) void r2iq_fs_kernel(
         }
     }
     ST_INIT();
+    // No wait for the loads above ahead of the loop.  They are still pending in the compiler's
+    // counters at the loop header, so its waits in the loop are conservative (vmcnt(N) in front of
+    // uses of cr and cp, vmcnt(0) in front of I2's lane factors, which is also what waits for the
+    // input prefetch).  An s_waitcnt in inline asm changes none of them (the compiler does not
+    // read it); __builtin_amdgcn_s_waitcnt here removes them all and moves the prefetch's wait into
+    // the next frame's F0, and measured 1.2-1.8 us of 200 slower (profiles/cached_p_pairs).
 
     auto frame = [&](auto phase) __attribute__((always_inline)) {
         constexpr bool PB = decltype(phase)::value;
@@ -413,11 +442,17 @@ __global__ __launch_bounds__(NT, 4) void r2iq_fs_kernel(
         if constexpr (PB && SCHED == kSchedSteal)
             if (qw) fsch.peek();
         // ---- F2 (R16, NS256) on column c: Z[c + 256 k] in v[k] ----
-        // The split's P loads (bin pairs p, 15 - p; 8 bytes per bin) run a pair ahead of their
-        // use, the first issued before F2 so that its reads and arithmetic cover the L2 latency
-        // (an empty asm with a memory clobber pins each group; the compiler's own schedule waits
-        // for every pair right after issuing it).  Issuing the first pair after the register-held
-        // ones before F2 instead measured -2.4 to +0.9 % (fs_first_uncached_p_before_f2_NEUTRAL.txt).
+        // The split's P (bin pairs p, 15 - p; 8 bytes per bin) comes from the registers cp[] for
+        // the pairs below CPP and from the table for the rest, whose loads run a pair ahead of
+        // their use (an empty asm with a memory clobber pins each group; the compiler's own
+        // schedule waits for every pair right after issuing it).  Pair 0's load is issued here,
+        // before F2, so that F2's reads and arithmetic cover its L2 latency; that is a load only
+        // where CPP is 0 (ZR = 0, +-2, the NCO / CS16 outputs, the queue and stealing schedules).
+        // With pairs in registers the first load left goes out at the top of the split: before F2
+        // it holds four more VGPRs across the pass, which is what keeping the pair costs (so at
+        // |ZR| >= 4 the pair is kept, and at |ZR| = 3 either form of pair 7 spills), and it measured
+        // -2.4 to +0.9 % with three loads left (fs_first_uncached_p_before_f2_NEUTRAL.txt) and no
+        // better than the split's top with one (profiles/cached_p_pairs).
         const __amdgpu_buffer_rsrc_t rpq = buf_rsrc(pqf + z);
         unsigned t16;
         if constexpr (PK) {
