@@ -103,6 +103,12 @@ SIGNATURES = {
     "sddc_ddc_channel_tone_device": (_I, [_P, _P, _SZ, _P, _I, _SZ, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _P]),
     "sddc_ddc_channel_tone_host": (_I, [_P, _P, _SZ, _P, _I, _SZ, _SZ, _P, _SZ, _P, _P, _P, _P, _P]),
     "sddc_ddc_internal_chtone_set_position": (_I, [_P, ctypes.c_uint64]),
+    "sddc_ddc_dcs_codeword": (_I, [_I, _P]),
+    "sddc_ddc_dcs_window": (_I, [ctypes.c_double, ctypes.c_double, _P, _P]),
+    "sddc_ddc_set_channel_dcs_decoder": (_I, [_P, _P, _I, _P, _I, ctypes.c_uint32, _I, _I, _I, _I, _I, _I, _I, _I]),
+    "sddc_ddc_channel_dcs_reset": (_I, [_P]),
+    "sddc_ddc_channel_dcs_device": (_I, [_P, _P, _SZ, _P, _I, _SZ, _SZ, _P, _SZ, _P, _P, _P, _P, _P]),
+    "sddc_ddc_channel_dcs_host": (_I, [_P, _P, _SZ, _P, _I, _SZ, _SZ, _P, _SZ, _P, _P, _P, _P]),
     "sddc_ddc_register_host": (_I, [_P, _P, _SZ]),
     "sddc_ddc_unregister_host": (_I, [_P, _P]),
     # include/sddc_fft.h

@@ -795,5 +795,66 @@ void R2iq::channel_tone(const void *sense, bool sense16, const void *audio, bool
     }
 }
 
+// The channel DCS decoder: dcs_math.h's stream, sample by sample; a window's decode when it completes.
+void R2iq::channel_dcs(const void *sense, bool sense16, const void *audio, bool in16, int nch, size_t nsamp,
+                       size_t sense_stride, size_t in_stride, const uint32_t *cws, int ncodes, const int32_t *params,
+                       uint32_t word, const uint32_t *counts, int window, int e_open, int e_close, int attack, int hang,
+                       uint64_t pos, DcsChannel *state, void *out, bool out16, size_t out_stride, int32_t *code_out,
+                       uint32_t *open, uint32_t *count, uint32_t *info)
+{
+    using namespace dcs;
+    const uint32_t WB = (uint32_t)(kDcsBlock * window);
+    for (int c = 0; c < nch; c++) {
+        const float *sf = static_cast<const float *>(sense) + (size_t)c * sense_stride;
+        const int16_t *ss = static_cast<const int16_t *>(sense) + (size_t)c * sense_stride;
+        const float *xf = static_cast<const float *>(audio) + (size_t)c * in_stride;
+        const int16_t *xs = static_cast<const int16_t *>(audio) + (size_t)c * in_stride;
+        float *yf = static_cast<float *>(out) + (size_t)c * out_stride;
+        int16_t *ys = static_cast<int16_t *>(out) + (size_t)c * out_stride;
+        const int code = params[3 * c], invert = params[3 * c + 1];
+        const uint32_t eye = (uint32_t)params[3 * c + 2];
+        DcsChannel &st = state[c];
+        uint32_t n = (uint32_t)(pos % (uint64_t)WB);   // the window-local index
+        uint32_t cnt = 0;
+        for (size_t i = 0; i < nsamp; i++) {
+            const int s = sense16 ? dcs_sign_s16((int)ss[i]) : dcs_sign(sf[i]);
+            const uint32_t m = dcs_subbin(word, n);
+            if (m < (uint32_t)kDcsSubBins) st.S[m] += s;
+            const uint32_t g = code == kDcsOff ? 1u : st.open;
+            if (audio) {
+                if (out16) {
+                    ys[i] = g ? demod::demod_s16(in16 ? (float)xs[i] : xf[i]) : (int16_t)0;
+                } else if (!g) {
+                    yf[i] = 0.f;
+                } else if (in16) {
+                    yf[i] = (float)xs[i];
+                } else {
+                    __builtin_memcpy(&yf[i], &xf[i], 4);   // the stored word: a NaN keeps its payload
+                }
+            }
+            cnt += g;
+            if (++n < WB) continue;
+            n = 0;
+            // the window is complete
+            uint32_t Q, d;
+            int t, best;
+            dcs_window(st.S, cws, ncodes, code, invert, &Q, &t, &best, &d);
+            bool u, v;
+            dcs_flags(Q, counts[t], d, eye, (uint32_t)e_open, (uint32_t)e_close, &u, &v);
+            squelch::squelch_step(u, v, (uint32_t)attack, (uint32_t)hang, &st.r, &st.n, &st.open);
+            st.code = v ? best : -1;
+            st.q = Q;
+            st.nt = counts[t];
+            st.d = d;
+            st.t = (uint32_t)t;
+            for (int32_t &x : st.S) x = 0;
+        }
+        if (code_out) code_out[c] = st.code;
+        if (open) open[c] = code == kDcsOff ? 1u : st.open;
+        if (count) count[c] = cnt;
+        if (info) info[4 * c] = st.q, info[4 * c + 1] = st.nt, info[4 * c + 2] = st.d, info[4 * c + 3] = st.t;
+    }
+}
+
 }  // namespace cpu
 }  // namespace sddc

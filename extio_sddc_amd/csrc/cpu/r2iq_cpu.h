@@ -29,6 +29,7 @@
 #include "../demod_math.h"
 #include "../squelch_math.h"
 #include "../tone_math.h"
+#include "../dcs_math.h"
 #include "fft_avx2.hpp"
 
 namespace sddc {
@@ -166,6 +167,22 @@ public:
                              const float *thr, int window, int attack, int hang, uint64_t pos, ToneChannel *state, void *out,
                              bool out16, size_t out_stride, int32_t *tone, uint32_t *open, uint32_t *count, float *level,
                              float *powers);
+    // The channel DCS decoder (sddc_ddc.h, sddc_ddc_channel_dcs_host; dcs_math.h): the definition's loop, sample
+    // by sample.  The streams as in channel_tone.  cws: [ncodes]; params: [nch][3] = (code, invert, eye); word:
+    // the bit phase word; counts: [8] = N[t]; window: W; pos: the stream index of the call's first sample; state:
+    // [nch], before the call and replaced by the one after it; code, open, count: null or [nch]; info: null or
+    // [nch][4].
+    struct DcsChannel {
+        uint32_t r = 0, n = 0, open = 0;   // the gate after the last completed window
+        int32_t code = -1;                 // the last completed window's: the best index where v held, Q, N, d, t
+        uint32_t q = 0, nt = 0, d = 0, t = 0;
+        int32_t S[dcs::kDcsSubBins] = {};  // the unfinished window's sub-bin sums
+    };
+    static void channel_dcs(const void *sense, bool sense16, const void *audio, bool in16, int nch, size_t nsamp,
+                            size_t sense_stride, size_t in_stride, const uint32_t *cws, int ncodes, const int32_t *params,
+                            uint32_t word, const uint32_t *counts, int window, int e_open, int e_close, int attack, int hang,
+                            uint64_t pos, DcsChannel *state, void *out, bool out16, size_t out_stride, int32_t *code,
+                            uint32_t *open, uint32_t *count, uint32_t *info);
     // demod_math.h's routines on arrays (the accuracy sweeps of tests/test_channel_demod_cpu.py)
     static void demod_angle_n(const float *im, const float *re, size_t n, float *out);
     static void demod_sincos_n(const uint32_t *words, size_t n, float *c, float *s);

@@ -350,6 +350,25 @@ hipError_t launch_channel_tone(const KernelTables &t, const void *d_sense, int s
                                size_t out_stride, int *d_tone, uint32_t *d_open, uint32_t *d_count, float *d_level,
                                float *d_powers, int accumulate, int max_wgs, int device, hipStream_t s);
 
+// Channel DCS decoder (ddc_channel_dcs.hip, sddc_ddc_channel_dcs_device): one launch set of the sign
+// sub-bins, the bit sums, the match and the gate (dcs_math.h) over nch real sense streams (F32 or S16) and,
+// where d_audio is not null, their audio streams (F32 or S16 in and out); strides in samples.  pos: the
+// stream index of the first sample; nsamp at most kDcsMaxLaunch.  d_cws: [ncodes] codewords; d_params:
+// [nch][3] ints (code, invert, eye); word: the bit phase word; counts: the host's [8] N[t]; d_state_in /
+// d_state_out: [nch][kDcsStateWords] words before / after (two buffers); d_scratch: [nch][windows that hold
+// a sample][4] words; d_code, d_open, d_count: null or [nch]; d_info: null or [nch][4]; accumulate: d_count
+// holds earlier launches of the same call and is added to; ballot: the windows kernel forms the sub-bin sums by
+// ballots and popcounts instead of LDS atomics (the same integers).  Two or three launches on s; max_wgs > 0
+// caps their grids (tests).  The caller has checked the strides and the alignment of the bases to a sample.
+constexpr int kDcsStateWords = 200;
+constexpr size_t kDcsMaxLaunch = (size_t)1 << 28;
+hipError_t launch_channel_dcs(const KernelTables &t, const void *d_sense, int sense_s16, size_t sense_stride, const void *d_audio,
+                              int in_s16, int nch, size_t nsamp, size_t in_stride, uint64_t pos, const uint32_t *d_cws, int ncodes,
+                              const int *d_params, uint32_t word, const uint32_t *counts, int window, int e_open, int e_close,
+                              int attack, int hang, const uint32_t *d_state_in, uint32_t *d_state_out, uint32_t *d_scratch,
+                              void *d_out, int out_s16, size_t out_stride, int *d_code, uint32_t *d_open, uint32_t *d_count,
+                              uint32_t *d_info, int accumulate, int ballot, int max_wgs, int device, hipStream_t s);
+
 // batched FFTs (fft_batch.hip, include/sddc_fft.h); fft_prepare fills the device's twiddle
 // table once (synchronises s the first time)
 hipError_t fft_prepare(hipStream_t s);

@@ -564,6 +564,67 @@ struct ChannelTone {
     }
 };
 
+// The state of the channel DCS decoder (sddc_ddc_channel_dcs_*; dcs_math.h): the codewords [ncodes] and the
+// per-channel (code, invert, eye) [nch][3] (empty = off) with their device copies, the handle's phase word,
+// window, N[t], error limits, attack, hang and formats, the stream position (host) and each channel's state as
+// [nch][kDcsStateWords] words in two device buffers that swap per launch set, as ChannelTone's do; d_scratch
+// holds four words per channel and window of a launch set, grown on demand.  A CPU handle keeps the state in
+// state_h.  d_sense / d_in / d_out / d_side are the host call's device buffers.  All under the handle's mu.
+struct ChannelDcs {
+    static constexpr int kDefaultRunBlocks = 4096;
+    std::vector<uint32_t> cws;
+    std::vector<int32_t> params;
+    uint32_t word = 0, counts[sddc::dcs::kDcsPhases] = {};
+    int nch = 0, ncodes = 0, window = 0, e_open = 0, e_close = 0, attack = 0, hang = 0, sense_fmt = 0, in_fmt = 0, out_fmt = 0;
+    uint64_t pos = 0;
+    uint32_t *d_cws = nullptr;
+    int32_t *d_params = nullptr;
+    uint32_t *d_state[2] = {};
+    int cur = 0;
+    uint32_t *d_scratch = nullptr;
+    size_t scratch_cap = 0;
+    std::vector<sddc::cpu::R2iq::DcsChannel> state_h;
+    Readers readers;
+    int max_wgs = 0, run_blocks = 0;   // SDDC_DDC_PARAM_CHDCS_MAX_WGS, _RUN_BLOCKS (0: kDefaultRunBlocks)
+    int ballot = 0;                    // SDDC_DDC_PARAM_CHDCS_BALLOT
+    void *d_sense = nullptr, *d_in = nullptr, *d_out = nullptr;
+    uint32_t *d_side = nullptr;        // [nch] code, [nch] open, [nch] count, [nch][4] info
+    size_t sense_cap = 0, in_cap = 0, out_cap = 0, side_cap = 0;   // bytes, bytes, bytes, words
+
+    size_t state_words() const { return (size_t)nch * sddc::kDcsStateWords; }
+    void clear()
+    {
+        cws.clear();
+        params.clear();
+        word = 0;
+        nch = ncodes = window = e_open = e_close = attack = hang = sense_fmt = in_fmt = out_fmt = 0;
+        pos = 0;
+        state_h.clear();
+        if (d_cws) (void)hipFree(d_cws);
+        if (d_params) (void)hipFree(d_params);
+        d_cws = nullptr;
+        d_params = nullptr;
+        for (uint32_t *&p : d_state) {
+            if (p) (void)hipFree(p);
+            p = nullptr;
+        }
+        cur = 0;
+    }
+    void free_all()
+    {
+        clear();
+        if (d_scratch) (void)hipFree(d_scratch);
+        if (d_sense) (void)hipFree(d_sense);
+        if (d_in) (void)hipFree(d_in);
+        if (d_out) (void)hipFree(d_out);
+        if (d_side) (void)hipFree(d_side);
+        d_scratch = d_side = nullptr;
+        d_sense = d_in = d_out = nullptr;
+        scratch_cap = sense_cap = in_cap = out_cap = side_cap = 0;
+        readers.clear();
+    }
+};
+
 }  // namespace
 
 struct sddc_ddc {
@@ -738,6 +799,7 @@ struct sddc_ddc {
     ChannelBlanker chnb;
     ChannelSquelch chsq;
     ChannelTone chtone;
+    ChannelDcs chdcs;
 
     // CPU handle (device SDDC_DDC_DEVICE_CPU): the AVX2 backend; no HIP object above exists
     std::unique_ptr<sddc::cpu::R2iq> cpu;
@@ -1095,6 +1157,7 @@ int sddc_ddc_destroy(sddc_ddc_t *h)
         (void)h->chnb.readers.sync();
         (void)h->chsq.readers.sync();
         (void)h->chtone.readers.sync();
+        (void)h->chdcs.readers.sync();
         if (h->d_tables) (void)hipFree(h->d_tables);
         for (auto &sl : h->hs) {
             if (sl.d_in) (void)hipFree(sl.d_in);
@@ -1134,6 +1197,7 @@ int sddc_ddc_destroy(sddc_ddc_t *h)
         h->chnb.free_all();
         h->chsq.free_all();
         h->chtone.free_all();
+        h->chdcs.free_all();
         if (h->fsa.h_ring) (void)hipHostFree(h->fsa.h_ring);   // its writers were waited for above
         h->readers.clear();
         h->ch_readers.clear();
@@ -1707,6 +1771,19 @@ int sddc_ddc_internal_set_param(sddc_ddc_t *h, int param, int value)
         if (value < 0 || value > (1 << 20))
             return fail(SDDC_ERR_ARG, "channel tone detector run length %d outside 0..2^20 blocks", value);
         h->chtone.run_blocks = value;
+        return SDDC_OK;
+    case SDDC_DDC_PARAM_CHDCS_MAX_WGS:
+        if (value < 0) return fail(SDDC_ERR_ARG, "channel DCS decoder workgroup cap %d is negative", value);
+        h->chdcs.max_wgs = value;
+        return SDDC_OK;
+    case SDDC_DDC_PARAM_CHDCS_RUN_BLOCKS:
+        if (value < 0 || value > (1 << 20))
+            return fail(SDDC_ERR_ARG, "channel DCS decoder run length %d outside 0..2^20 blocks", value);
+        h->chdcs.run_blocks = value;
+        return SDDC_OK;
+    case SDDC_DDC_PARAM_CHDCS_BALLOT:
+        if (value != 0 && value != 1) return fail(SDDC_ERR_ARG, "channel DCS decoder ballot route %d is not 0 or 1", value);
+        h->chdcs.ballot = value;
         return SDDC_OK;
     default:
         return fail(SDDC_ERR_ARG, "unknown parameter %d", param);
@@ -4067,6 +4144,312 @@ int sddc_ddc_channel_tone_host(sddc_ddc_t *h, const void *sense, size_t sense_st
         if (count) HIP_TRY(hipMemcpyAsync(count, d_count, n * 4, hipMemcpyDeviceToHost, h->stream));
         if (level) HIP_TRY(hipMemcpyAsync(level, d_level, n * 8, hipMemcpyDeviceToHost, h->stream));
         if (powers) HIP_TRY(hipMemcpyAsync(powers, d_powers, n * (size_t)st.ntones * 4, hipMemcpyDeviceToHost, h->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(h->stream));   // also after a failed launch: the caller's input is free again
+    return rc;
+}
+
+/* ---- channel DCS decoder: streaming per-channel digital code squelch ----------------------------- */
+static_assert(SDDC_DDC_DCS_BLOCK == sddc::dcs::kDcsBlock && SDDC_DDC_DCS_MAX_CODES == sddc::dcs::kDcsMaxCodes &&
+                  SDDC_DDC_DCS_MAX_WINDOW == sddc::dcs::kDcsMaxWindow && SDDC_DDC_DCS_MAX_ATTACK == sddc::dcs::kDcsMaxAttack &&
+                  SDDC_DDC_DCS_MAX_HANG == sddc::dcs::kDcsMaxHang && SDDC_DDC_DCS_MAX_ERRORS == sddc::dcs::kDcsMaxErrors &&
+                  SDDC_DDC_DCS_MAX_EYE == sddc::dcs::kDcsMaxEye && SDDC_DDC_DCS_ANY == sddc::dcs::kDcsAny &&
+                  SDDC_DDC_DCS_OFF == sddc::dcs::kDcsOff && SDDC_DDC_DCS_MAX_WORD == sddc::dcs::kDcsMaxWord,
+              "the arithmetic header's constants are the ABI's");
+static_assert(sizeof(sddc::cpu::R2iq::DcsChannel) == (size_t)sddc::kDcsStateWords * 4, "the CPU state holds what the device's does");
+
+int sddc_ddc_dcs_codeword(int code, uint32_t *cw)
+{
+    if (!cw) return fail(SDDC_ERR_ARG, "dcs_codeword: null cw");
+    if (code < 0 || code > 511) return fail(SDDC_ERR_ARG, "dcs_codeword: code %d outside 0..511 (three octal digits)", code);
+    *cw = sddc::dcs::dcs_codeword((uint32_t)code);
+    return SDDC_OK;
+}
+
+int sddc_ddc_dcs_window(double fs, double bitrate, uint32_t *word, int *blocks)
+{
+    if (!word || !blocks) return fail(SDDC_ERR_ARG, "dcs_window: null word or blocks");
+    if (!std::isfinite(fs) || !std::isfinite(bitrate) || !(fs > 0.0) || !(bitrate > 0.0))
+        return fail(SDDC_ERR_ARG, "dcs_window: %g bit/s at %g Hz are not finite positive rates", bitrate, fs);
+    const double w = std::nearbyint(bitrate / fs * 4294967296.0);
+    if (!(w >= 1.0) || !(w <= (double)SDDC_DDC_DCS_MAX_WORD))
+        return fail(SDDC_ERR_ARG, "dcs_window: %g bit/s at %g Hz is the phase word %g, outside 1..2^29", bitrate, fs, w);
+    const uint64_t wi = (uint64_t)w, num = (uint64_t)24 << 32, den = (uint64_t)SDDC_DDC_DCS_BLOCK * wi;
+    const uint64_t b = (num + den - 1) / den;
+    if (b > (uint64_t)SDDC_DDC_DCS_MAX_WINDOW)
+        return fail(SDDC_ERR_ARG, "dcs_window: %g bit/s at %g Hz needs %llu blocks, above %d", bitrate, fs, (unsigned long long)b,
+                    SDDC_DDC_DCS_MAX_WINDOW);
+    *word = (uint32_t)wi;
+    *blocks = (int)(b < 1 ? 1 : b);
+    return SDDC_OK;
+}
+
+int sddc_ddc_set_channel_dcs_decoder(sddc_ddc_t *h, const uint32_t *codewords, int ncodes, const int32_t *params, int nch,
+                                     uint32_t word, int window, int e_open, int e_close, int attack, int hang, int sense_format,
+                                     int in_format, int out_format)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    const bool off = !codewords || !params || nch == 0;
+    std::vector<uint32_t> cw;
+    std::vector<int32_t> pr;
+    if (!off) {
+        if (nch < 1 || nch > SDDC_DDC_MAX_CHANNELS)
+            return fail(SDDC_ERR_ARG, "channel DCS decoder: nch %d outside 1..%d", nch, SDDC_DDC_MAX_CHANNELS);
+        if (ncodes < 1 || ncodes > SDDC_DDC_DCS_MAX_CODES)
+            return fail(SDDC_ERR_ARG, "channel DCS decoder: ncodes %d outside 1..%d", ncodes, SDDC_DDC_DCS_MAX_CODES);
+        if (word < 1 || word > SDDC_DDC_DCS_MAX_WORD)
+            return fail(SDDC_ERR_ARG, "channel DCS decoder: the phase word %u is outside 1..2^29", word);
+        if (window < 1 || window > SDDC_DDC_DCS_MAX_WINDOW)
+            return fail(SDDC_ERR_ARG, "channel DCS decoder: window %d outside 1..%d blocks", window, SDDC_DDC_DCS_MAX_WINDOW);
+        if ((uint64_t)SDDC_DDC_DCS_BLOCK * (uint64_t)window * (uint64_t)word < ((uint64_t)24 << 32))
+            return fail(SDDC_ERR_ARG, "channel DCS decoder: a window of %d blocks holds fewer than 24 bits at the phase word %u", window,
+                        word);
+        if (e_open < 0 || e_open > e_close || e_close > SDDC_DDC_DCS_MAX_ERRORS)
+            return fail(SDDC_ERR_ARG, "channel DCS decoder: the error limits %d, %d are not 0 <= e_open <= e_close <= %d", e_open,
+                        e_close, SDDC_DDC_DCS_MAX_ERRORS);
+        if (attack < 1 || attack > SDDC_DDC_DCS_MAX_ATTACK)
+            return fail(SDDC_ERR_ARG, "channel DCS decoder: attack %d outside 1..%d windows", attack, SDDC_DDC_DCS_MAX_ATTACK);
+        if (hang < 0 || hang > SDDC_DDC_DCS_MAX_HANG)
+            return fail(SDDC_ERR_ARG, "channel DCS decoder: hang %d outside 0..%d windows", hang, SDDC_DDC_DCS_MAX_HANG);
+        for (int fmt : {sense_format, in_format, out_format})
+            if (fmt != SDDC_DDC_AUDIO_F32 && fmt != SDDC_DDC_AUDIO_S16)
+                return fail(SDDC_ERR_ARG, "channel DCS decoder: unknown sample format %d", fmt);
+        for (int i = 0; i < ncodes; i++)
+            if (codewords[i] >> 23)
+                return fail(SDDC_ERR_ARG, "channel DCS decoder: codeword %d = 0x%x has a bit above its 23", i, codewords[i]);
+        for (int c = 0; c < nch; c++) {
+            const int32_t code = params[3 * c], inv = params[3 * c + 1], eye = params[3 * c + 2];
+            if (code < SDDC_DDC_DCS_OFF || code >= ncodes)
+                return fail(SDDC_ERR_ARG, "channel DCS decoder: the code %d of channel %d is no index below ncodes = %d, ANY or OFF", code,
+                            c, ncodes);
+            if (inv != 0 && inv != 1) return fail(SDDC_ERR_ARG, "channel DCS decoder: invert %d of channel %d is not 0 or 1", inv, c);
+            if (eye < 0 || eye > SDDC_DDC_DCS_MAX_EYE)
+                return fail(SDDC_ERR_ARG, "channel DCS decoder: eye %d of channel %d outside 0..%d", eye, c, SDDC_DDC_DCS_MAX_EYE);
+        }
+        try {
+            cw.assign(codewords, codewords + ncodes);
+            pr.assign(params, params + 3 * (size_t)nch);
+        } catch (const std::exception &ex) {
+            return fail(SDDC_ERR_NOMEM, "channel DCS decoder: %s", ex.what());
+        }
+    }
+    std::lock_guard<std::mutex> lk(h->mu);
+    ChannelDcs &st = h->chdcs;
+    if (h->cpu) {
+        st.clear();
+        if (off) return SDDC_OK;
+        try {
+            st.state_h.assign((size_t)nch, sddc::cpu::R2iq::DcsChannel());
+        } catch (const std::exception &ex) {
+            st.clear();
+            return fail(SDDC_ERR_NOMEM, "channel DCS decoder: %s", ex.what());
+        }
+    } else {
+        DeviceGuard g(h->device);
+        HIP_TRY(g.err);
+        HIP_TRY(st.readers.sync());   // earlier launches, on any stream, may still use the state
+        st.clear();                   // a failed upload leaves the stage off
+        if (off) return SDDC_OK;
+        const size_t nstate = (size_t)nch * sddc::kDcsStateWords;
+        hipError_t e = hipMalloc(&st.d_cws, cw.size() * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMalloc(&st.d_params, pr.size() * sizeof(int32_t));
+        for (uint32_t *&p : st.d_state)
+            if (e == hipSuccess) e = hipMalloc(&p, nstate * sizeof(uint32_t));
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            st.clear();
+            return fail(SDDC_ERR_NOMEM, "channel DCS decoder: no device memory for %d channels", nch);
+        }
+        e = hipMemcpy(st.d_cws, cw.data(), cw.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(st.d_params, pr.data(), pr.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+        // zeroed on the handle's stream and waited for: the first launch may be on any stream
+        for (uint32_t *p : st.d_state)
+            if (e == hipSuccess) e = hipMemsetAsync(p, 0, nstate * sizeof(uint32_t), h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) {
+            st.clear();
+            HIP_TRY(e);
+        }
+    }
+    st.cws = std::move(cw);
+    st.params = std::move(pr);
+    st.word = word;
+    sddc::dcs::dcs_count(word, window, st.counts);
+    st.nch = nch;
+    st.ncodes = ncodes;
+    st.window = window;
+    st.e_open = e_open;
+    st.e_close = e_close;
+    st.attack = attack;
+    st.hang = hang;
+    st.sense_fmt = sense_format;
+    st.in_fmt = in_format;
+    st.out_fmt = out_format;
+    st.pos = 0;
+    return SDDC_OK;
+}
+
+int sddc_ddc_channel_dcs_reset(sddc_ddc_t *h)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    ChannelDcs &st = h->chdcs;
+    if (st.params.empty()) return fail(SDDC_ERR_STATE, "channel DCS reset: no decoder set");
+    if (h->cpu) {
+        std::fill(st.state_h.begin(), st.state_h.end(), sddc::cpu::R2iq::DcsChannel());
+    } else {
+        DeviceGuard g(h->device);
+        HIP_TRY(g.err);
+        HIP_TRY(st.readers.sync());   // earlier launches, on any stream, may still use the state
+        HIP_TRY(hipMemsetAsync(st.d_state[st.cur], 0, st.state_words() * sizeof(uint32_t), h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));   // the next launch may be on any stream
+    }
+    st.pos = 0;
+    return SDDC_OK;
+}
+
+// the checks both calls share (under h->mu)
+static int check_chdcs_args(const sddc_ddc_t *h, const void *sense, size_t sense_stride, const void *in, int nch, size_t nsamp,
+                            size_t in_stride, const void *out, size_t out_stride, const void *code, const void *open,
+                            const void *count, const void *info)
+{
+    const ChannelDcs &st = h->chdcs;
+    if (st.params.empty()) return fail(SDDC_ERR_STATE, "channel DCS decoder: no decoder set");
+    if (nch != st.nch)
+        return fail(SDDC_ERR_STATE, "channel DCS decoder: the decoder is set for %d channels, the call has %d", st.nch, nch);
+    if (nsamp == 0 || nsamp > ((size_t)1 << 40)) return fail(SDDC_ERR_ARG, "nsamp must be in 1..2^40 (got %zu)", nsamp);
+    if (!sense) return fail(SDDC_ERR_ARG, "null sense buffer");
+    if (nch > 1 && sense_stride < nsamp)
+        return fail(SDDC_ERR_ARG, "sense_stride must be >= nsamp (got %zu, nsamp %zu)", sense_stride, nsamp);
+    const uintptr_t ss = st.sense_fmt == SDDC_DDC_AUDIO_S16 ? 2 : 4;
+    if (((uintptr_t)sense & (ss - 1)) != 0) return fail(SDDC_ERR_ARG, "the sense buffer must be %d-byte aligned", (int)ss);
+    if ((((uintptr_t)code | (uintptr_t)open | (uintptr_t)count | (uintptr_t)info) & 3) != 0)
+        return fail(SDDC_ERR_ARG, "the side outputs must be 4-byte aligned");
+    if (!in && out) return fail(SDDC_ERR_ARG, "an output without audio");
+    if (in && !out) return fail(SDDC_ERR_ARG, "audio without an output");
+    if (!in) return SDDC_OK;
+    if (nch > 1 && in_stride < nsamp) return fail(SDDC_ERR_ARG, "in_stride must be >= nsamp (got %zu, nsamp %zu)", in_stride, nsamp);
+    if (nch > 1 && out_stride < nsamp)
+        return fail(SDDC_ERR_ARG, "out_stride must be >= nsamp (got %zu, nsamp %zu)", out_stride, nsamp);
+    const uintptr_t is = st.in_fmt == SDDC_DDC_AUDIO_S16 ? 2 : 4, os = st.out_fmt == SDDC_DDC_AUDIO_S16 ? 2 : 4;
+    if (((uintptr_t)in & (is - 1)) != 0) return fail(SDDC_ERR_ARG, "the input must be %d-byte aligned", (int)is);
+    if (((uintptr_t)out & (os - 1)) != 0) return fail(SDDC_ERR_ARG, "the output must be %d-byte aligned", (int)os);
+    const uintptr_t ia = (uintptr_t)in, oa = (uintptr_t)out, sa = (uintptr_t)sense;
+    const uintptr_t ib = ia + ((uintptr_t)(nch - 1) * (nch > 1 ? in_stride : 0) + nsamp) * is;
+    const uintptr_t ob = oa + ((uintptr_t)(nch - 1) * (nch > 1 ? out_stride : 0) + nsamp) * os;
+    const uintptr_t sb = sa + ((uintptr_t)(nch - 1) * (nch > 1 ? sense_stride : 0) + nsamp) * ss;
+    if (ia < ob && oa < ib) return fail(SDDC_ERR_ARG, "the input and the output overlap");
+    if (sa < ob && oa < sb) return fail(SDDC_ERR_ARG, "the sense buffer and the output overlap");
+    return SDDC_OK;
+}
+
+// The call in launch sets of at most run_blocks blocks per channel, rounded down to whole windows (the
+// scratch holds four words per channel and window of a set, and the kernels index a set with an int).
+static int chdcs_launch(sddc_ddc_t *h, const void *d_sense, size_t sense_stride, const void *d_in, int nch, size_t nsamp,
+                        size_t in_stride, void *d_out, size_t out_stride, int32_t *d_code, uint32_t *d_open, uint32_t *d_count,
+                        uint32_t *d_info, hipStream_t s)
+{
+    ChannelDcs &st = h->chdcs;
+    const size_t B = SDDC_DDC_DCS_BLOCK, W = (size_t)st.window, WB = W * B;
+    const size_t run_blocks = (size_t)(st.run_blocks > 0 ? st.run_blocks : ChannelDcs::kDefaultRunBlocks);
+    const size_t run_windows = run_blocks / W > 0 ? run_blocks / W : 1;
+    const size_t hs0 = (size_t)(st.pos % WB), windows = (hs0 + nsamp + WB - 1) / WB;
+    const size_t need = (size_t)nch * (windows < run_windows ? windows : run_windows) * 4;
+    if (need > st.scratch_cap) {
+        HIP_TRY(st.readers.sync());   // an earlier launch may still use the scratch
+        if (int rc = grow_device_buffer(&st.d_scratch, &st.scratch_cap, need, "channel DCS decoder", "scratch words")) return rc;
+    }
+    HIP_TRY(st.readers.order_before(s));
+    const bool s16 = st.sense_fmt == SDDC_DDC_AUDIO_S16, in16 = st.in_fmt == SDDC_DDC_AUDIO_S16, out16 = st.out_fmt == SDDC_DDC_AUDIO_S16;
+    const size_t ss = s16 ? 2 : 4, is = in16 ? 2 : 4, os = out16 ? 2 : 4;
+    hipError_t e = hipSuccess;
+    for (size_t done = 0; done < nsamp && e == hipSuccess;) {
+        const size_t hs = (size_t)(st.pos % WB);
+        size_t n = nsamp - done;
+        if (n > run_windows * WB - hs) n = run_windows * WB - hs;
+        e = sddc::launch_channel_dcs(h->tables, static_cast<const char *>(d_sense) + done * ss, s16, sense_stride,
+                                     d_in ? static_cast<const char *>(d_in) + done * is : nullptr, in16, nch, n, in_stride, st.pos,
+                                     st.d_cws, st.ncodes, st.d_params, st.word, st.counts, st.window, st.e_open, st.e_close, st.attack,
+                                     st.hang, st.d_state[st.cur], st.d_state[st.cur ^ 1], st.d_scratch,
+                                     d_in ? static_cast<char *>(d_out) + done * os : nullptr, out16, out_stride, d_code, d_open, d_count,
+                                     d_info, done > 0, st.ballot, st.max_wgs, h->device, s);
+        if (e != hipSuccess) break;
+        st.cur ^= 1;
+        st.pos += n;
+        done += n;
+    }
+    const hipError_t er = st.readers.record(s);   // whatever was enqueued stays ordered
+    HIP_TRY(e);
+    HIP_TRY(er);
+    return SDDC_OK;
+}
+
+int sddc_ddc_channel_dcs_device(sddc_ddc_t *h, const void *d_sense, size_t sense_stride, const void *d_audio, int nch,
+                                size_t nsamp, size_t in_stride, void *d_out, size_t out_stride, int32_t *d_code, uint32_t *d_open,
+                                uint32_t *d_count, uint32_t *d_info, void *hip_stream)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->cpu) return fail(SDDC_ERR_STATE, "channel_dcs_device: a CPU handle has no device path");
+    if (int rc = check_chdcs_args(h, d_sense, sense_stride, d_audio, nch, nsamp, in_stride, d_out, out_stride, d_code, d_open, d_count,
+                                  d_info))
+        return rc;
+    DeviceGuard g(h->device);
+    HIP_TRY(g.err);
+    return chdcs_launch(h, d_sense, sense_stride, d_audio, nch, nsamp, in_stride, d_out, out_stride, d_code, d_open, d_count, d_info,
+                        (hipStream_t)hip_stream);
+}
+
+int sddc_ddc_channel_dcs_host(sddc_ddc_t *h, const void *sense, size_t sense_stride, const void *audio, int nch, size_t nsamp,
+                              size_t in_stride, void *out, size_t out_stride, int32_t *code, uint32_t *open, uint32_t *count,
+                              uint32_t *info)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (int rc = check_chdcs_args(h, sense, sense_stride, audio, nch, nsamp, in_stride, out, out_stride, code, open, count, info)) return rc;
+    ChannelDcs &st = h->chdcs;
+    const bool s16 = st.sense_fmt == SDDC_DDC_AUDIO_S16, in16 = st.in_fmt == SDDC_DDC_AUDIO_S16, out16 = st.out_fmt == SDDC_DDC_AUDIO_S16;
+    if (h->cpu) {
+        sddc::cpu::R2iq::channel_dcs(sense, s16, audio, in16, nch, nsamp, nch > 1 ? sense_stride : 0, nch > 1 ? in_stride : 0,
+                                     st.cws.data(), st.ncodes, st.params.data(), st.word, st.counts, st.window, st.e_open, st.e_close,
+                                     st.attack, st.hang, st.pos, st.state_h.data(), out, out16, nch > 1 ? out_stride : 0, code, open,
+                                     count, info);
+        st.pos += nsamp;
+        return SDDC_OK;
+    }
+    DeviceGuard g(h->device);
+    HIP_TRY(g.err);
+    // the spans that hold every channel's samples and outputs
+    const size_t ss = s16 ? 2 : 4, is = in16 ? 2 : 4, os = out16 ? 2 : 4;
+    const size_t sense_bytes = ((size_t)(nch - 1) * (nch > 1 ? sense_stride : 0) + nsamp) * ss;
+    const size_t in_bytes = audio ? ((size_t)(nch - 1) * (nch > 1 ? in_stride : 0) + nsamp) * is : 0;
+    const size_t out_bytes = audio ? ((size_t)(nch - 1) * (nch > 1 ? out_stride : 0) + nsamp) * os : 0;
+    const size_t n = (size_t)nch;
+    if (int rc = grow_device_buffer(&st.d_sense, &st.sense_cap, sense_bytes, "channel_dcs_host", "sense bytes")) return rc;
+    if (audio) {
+        if (int rc = grow_device_buffer(&st.d_in, &st.in_cap, in_bytes, "channel_dcs_host", "input bytes")) return rc;
+        if (int rc = grow_device_buffer(&st.d_out, &st.out_cap, out_bytes, "channel_dcs_host", "output bytes")) return rc;
+    }
+    if (int rc = grow_device_buffer(&st.d_side, &st.side_cap, n * 7, "channel_dcs_host", "side outputs")) return rc;
+    int32_t *d_code = code ? reinterpret_cast<int32_t *>(st.d_side) : nullptr;
+    uint32_t *d_open = open ? st.d_side + n : nullptr, *d_count = count ? st.d_side + 2 * n : nullptr;
+    uint32_t *d_info = info ? st.d_side + 3 * n : nullptr;
+    HIP_TRY(hipMemcpyAsync(st.d_sense, sense, sense_bytes, hipMemcpyHostToDevice, h->stream));
+    if (audio) HIP_TRY(hipMemcpyAsync(st.d_in, audio, in_bytes, hipMemcpyHostToDevice, h->stream));
+    const int rc = chdcs_launch(h, st.d_sense, sense_stride, audio ? st.d_in : nullptr, nch, nsamp, in_stride, audio ? st.d_out : nullptr,
+                                out_stride, d_code, d_open, d_count, d_info, h->stream);
+    if (rc == SDDC_OK) {   // the streams alone: the caller's memory between them stays as it is
+        if (audio) {
+            if (nch == 1 || out_stride == nsamp)
+                HIP_TRY(hipMemcpyAsync(out, st.d_out, out_bytes, hipMemcpyDeviceToHost, h->stream));
+            else
+                HIP_TRY(hipMemcpy2DAsync(out, out_stride * os, st.d_out, out_stride * os, nsamp * os, n, hipMemcpyDeviceToHost,
+                                         h->stream));
+        }
+        if (code) HIP_TRY(hipMemcpyAsync(code, d_code, n * 4, hipMemcpyDeviceToHost, h->stream));
+        if (open) HIP_TRY(hipMemcpyAsync(open, d_open, n * 4, hipMemcpyDeviceToHost, h->stream));
+        if (count) HIP_TRY(hipMemcpyAsync(count, d_count, n * 4, hipMemcpyDeviceToHost, h->stream));
+        if (info) HIP_TRY(hipMemcpyAsync(info, d_info, n * 16, hipMemcpyDeviceToHost, h->stream));
     }
     HIP_TRY(hipStreamSynchronize(h->stream));   // also after a failed launch: the caller's input is free again
     return rc;

@@ -125,6 +125,21 @@ extern "C" {
  * length changes no output bit and no side output (tests). */
 #define SDDC_DDC_PARAM_CHTONE_RUN_BLOCKS 26
 
+/* SDDC_DDC_PARAM_CHDCS_MAX_WGS = n > 0: each of the channel DCS decoder's grids is at most n workgroups, as
+ * param 25 for the tone detector; 0 (default): full residency with a loop.  The grid changes no output bit
+ * and no side output (tests). */
+#define SDDC_DDC_PARAM_CHDCS_MAX_WGS 27
+
+/* SDDC_DDC_PARAM_CHDCS_RUN_BLOCKS = n in 1..2^20: a call of the channel DCS decoder is cut into launch sets
+ * of at most n blocks per channel, rounded down to whole windows (at least one); 0: 4096.  The run length
+ * changes no output bit and no side output (tests). */
+#define SDDC_DDC_PARAM_CHDCS_RUN_BLOCKS 28
+
+/* SDDC_DDC_PARAM_CHDCS_BALLOT = 1: the channel DCS decoder's windows kernel forms the sub-bin sums with wave
+ * ballots and masked popcounts instead of integer LDS atomics; 0 (default): atomics, the faster route as
+ * measured.  Both are sums of the same integers: the route changes no output bit and no side output (tests). */
+#define SDDC_DDC_PARAM_CHDCS_BALLOT 29
+
 int sddc_ddc_internal_set_param(sddc_ddc_t *h, int param, int value);
 /* Move the channel tone detector's stream position to pos, a multiple of 256 W (SDDC_ERR_ARG otherwise;
  * SDDC_ERR_STATE: no detector set): the unfinished window's sums and the unfinished block are cleared, the

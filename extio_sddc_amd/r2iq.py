@@ -214,6 +214,33 @@ def tone_window(seconds: float, fs: float) -> int:
     return int(b.value)
 
 
+DCS_BLOCK = 256                           # SDDC_DDC_DCS_BLOCK: the DCS decoder's block length B
+DCS_ANY, DCS_OFF = -1, -2                 # SDDC_DDC_DCS_ANY (match the whole table), _OFF (bypass)
+# the 104 standard DCS codes, as their three octal digits
+DCS_CODES = tuple("""023 025 026 031 032 036 043 047 051 053 054 065 071 072 073 074 114 115 116 122 125 131 132 134 143 145 152
+155 156 162 165 172 174 205 212 223 225 226 243 244 245 246 251 252 255 261 263 265 266 271 274 306 311 315 325 331 332 343 346
+351 356 364 365 371 411 412 413 423 431 432 445 446 452 454 455 462 464 465 466 503 506 516 523 526 532 546 565 606 612 624 627
+631 632 654 662 664 703 712 723 731 732 734 743 754""".split())
+
+
+def dcs_codeword(code) -> int:
+    """The 23-bit codeword (bit 0 first on the air) of a DCS code, given as its three octal digits ("023") or as
+    the integer 0..511 they spell (sddc_ddc_dcs_codeword): 023 is 0x763813."""
+    c = int(code, 8) if isinstance(code, str) else int(code)
+    cw = ctypes.c_uint32()
+    check(_lib.load().sddc_ddc_dcs_codeword(c, ctypes.addressof(cw)))
+    return int(cw.value)
+
+
+def dcs_window(fs: float, bitrate: float = 134.4):
+    """(word, blocks): the bit phase word round(bitrate / fs * 2^32) and the shortest window ceil(24 * 2^32 / (256
+    word)) in blocks of 256 samples (sddc_ddc_dcs_window); 8 kS/s gives 6 blocks, 48 kS/s 34."""
+    w = ctypes.c_uint32()
+    b = ctypes.c_int()
+    check(_lib.load().sddc_ddc_dcs_window(float(fs), float(bitrate), ctypes.addressof(w), ctypes.addressof(b)))
+    return int(w.value), int(b.value)
+
+
 def psd_to_dbfs(psd) -> np.ndarray:
     """R2iq.spectrum's output in dB relative to a full-scale real tone (amplitude 32768 reads
     32768^2 / 4 at its bin centre): 10 log10(4 psd / 32768^2); -inf where psd is 0."""
@@ -248,6 +275,7 @@ class R2iq:
         self._blanker = None  # (nch, format) of setChannelBlanker
         self._squelch = None  # (nch, sense, in_format, out_format) of setChannelSquelch
         self._tone = None     # (nch, ntones, sense_format, in_format, out_format) of setChannelToneDetector
+        self._dcs = None      # (nch, sense_format, in_format, out_format) of setChannelDcsDecoder
 
     # -- lifecycle --------------------------------------------------------
     @property
@@ -1152,6 +1180,113 @@ class R2iq:
                                                    None if d_out is None else d_out.data_ptr(), out_stride,
                                                    *(None if t is None else t.data_ptr() for _, t, _, _ in sides),
                                                    _stream_handle(stream)))
+
+    # -- channel DCS decoder -------------------------------------------------------
+    def setChannelDcsDecoder(self, codewords, params, word: int, window: int, e_open: int = 1, e_close: int = 2,
+                             attack: int = 1, hang: int = 0, fmt_sense: int = AUDIO_F32, fmt_in: int = AUDIO_F32,
+                             fmt_out: int = AUDIO_F32) -> None:
+        """The streaming digital code squelch of channel_dcs_host / channel_dcs_device: codewords is uint32
+        [ncodes], 1..128 23-bit codewords (dcs_codeword); params int32 [nch, 3] = (code, invert, eye): an index
+        into the table, DCS_ANY (match the whole table) or DCS_OFF (bypass, always open), whether the received
+        word is complemented before matching, and the eye 0..256 that 256 Q / N must reach.  word, window: the bit
+        phase word and the window in blocks of 256 samples (dcs_window); e_open <= e_close: 0..3 bit errors that
+        open and that keep open; attack: 1..255 windows before a channel opens; hang: 0..65535 windows it stays
+        open without the code; fmt_*: AUDIO_F32 or AUDIO_S16 of the sense stream, the audio and the output.
+        Every call zeroes the state and the stream position.  codewords=None turns the stage off."""
+        if codewords is None or np.size(codewords) == 0:
+            check(self._L.sddc_ddc_set_channel_dcs_decoder(self._h, None, 0, None, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0))
+            self._dcs = None
+            return
+        cw = np.ascontiguousarray(np.asarray(codewords, np.uint32).reshape(-1))
+        p = np.ascontiguousarray(np.asarray(params, np.int32))
+        if p.ndim != 2 or p.shape[1] != 3 or p.shape[0] < 1:
+            raise DDCError(-1, "params must be [nch, 3] = (code, invert, eye)")
+        if not 0 <= int(word) < 2 ** 32:
+            raise DDCError(-1, "word must be a uint32")
+        check(self._L.sddc_ddc_set_channel_dcs_decoder(self._h, cw.ctypes.data, cw.shape[0], p.ctypes.data, p.shape[0], int(word),
+                                                       int(window), int(e_open), int(e_close), int(attack), int(hang),
+                                                       int(fmt_sense), int(fmt_in), int(fmt_out)))
+        self._dcs = (p.shape[0], int(fmt_sense), int(fmt_in), int(fmt_out))
+
+    def resetChannelDcsDecoder(self) -> None:
+        """Zero every channel's state and the stream position: the next call starts a closed stream."""
+        check(self._L.sddc_ddc_channel_dcs_reset(self._h))
+
+    def channel_dcs_host(self, sense: np.ndarray, audio=None):
+        """The DCS decoder on host arrays: sense is float32 (AUDIO_S16 sense: int16) [nch, nsamp], any nsamp >= 1;
+        audio None (detect only) or float32 / int16 [nch, nsamp]; a single stream may drop the channel axis.
+        Returns a dict: out (float32 / int16 [nch, nsamp], None without audio), code (int32 [nch], the best table
+        index of the last completed window where it held the closing limits, else -1), open (uint32 [nch]), count
+        (uint32 [nch], this call's samples in open windows), info (uint32 [nch, 4] = Q, N, d, t of the last
+        completed window).  Keeps every channel's state for the next call."""
+        if self._dcs is None:
+            raise DDCError(-4, "no channel DCS decoder set")
+        nch, fs, fin, fout = self._dcs
+        s = np.asarray(sense, np.int16 if fs == AUDIO_S16 else np.float32)
+        if s.ndim == 1:
+            s = s[None, :]
+        s = np.ascontiguousarray(s)
+        if s.ndim != 2 or s.shape[1] < 1:
+            raise DDCError(-1, "sense must be [nch, nsamp] with nsamp >= 1")
+        n, nsamp = s.shape
+        a = out = None
+        if audio is not None:
+            a = np.asarray(audio, np.int16 if fin == AUDIO_S16 else np.float32)
+            if a.ndim == 1:
+                a = a[None, :]
+            a = np.ascontiguousarray(a)
+            if a.shape != s.shape:
+                raise DDCError(-1, "the audio must have the sense stream's [nch, nsamp]")
+            out = np.empty((n, nsamp), np.int16 if fout == AUDIO_S16 else np.float32)
+        code = np.empty(n, np.int32)
+        o = np.empty(n, np.uint32)
+        c = np.empty(n, np.uint32)
+        info = np.empty((n, 4), np.uint32)
+        check(self._L.sddc_ddc_channel_dcs_host(self._h, s.ctypes.data, nsamp, None if a is None else a.ctypes.data, n, nsamp,
+                                                nsamp, None if out is None else out.ctypes.data, nsamp, code.ctypes.data,
+                                                o.ctypes.data, c.ctypes.data, info.ctypes.data))
+        return {"out": out, "code": code, "open": o, "count": c, "info": info}
+
+    channel_dcs = channel_dcs_host
+
+    def channel_dcs_device(self, d_sense, sense_stride: int, d_audio, nch: int, nsamp: int, in_stride: int, d_out,
+                           out_stride: int, d_code=None, d_open=None, d_count=None, d_info=None, stream=None) -> None:
+        """The DCS decoder on device buffers: d_sense is a float32 (AUDIO_S16 sense: int16) device tensor, channel
+        c's nsamp samples at c * sense_stride; d_audio None (detect only, d_out None too) or the audio buffer of
+        the demodulator, the audio filter or the AGC, channel c's samples at c * in_stride, with d_out its gated
+        copy at c * out_stride; d_out must overlap neither input.  d_code, d_open, d_count: None or int32 device
+        tensors of nch values; d_info: None or int32 [nch, 4].  Enqueued on `stream` like process_device; the calls
+        of one handle run in call order."""
+        import torch
+        if self._dcs is None:
+            raise DDCError(-4, "no channel DCS decoder set")
+        _, fs, fin, fout = self._dcs
+        if nch < 1 or nsamp < 1:
+            raise DDCError(-1, "nch and nsamp must be >= 1")
+        if (d_audio is None) != (d_out is None):
+            raise DDCError(-1, "d_audio and d_out go together")
+        sides = (("d_code", d_code, torch.int32, nch), ("d_open", d_open, torch.int32, nch), ("d_count", d_count, torch.int32, nch),
+                 ("d_info", d_info, torch.int32, 4 * nch))
+        if not all(t is None or t.is_cuda for t in (d_sense, d_audio, d_out, d_code, d_open, d_count, d_info)):
+            raise DDCError(-1, "device path needs device tensors")
+        bufs = [("d_sense", d_sense, sense_stride, torch.int16 if fs == AUDIO_S16 else torch.float32)]
+        if d_audio is not None:
+            bufs += [("d_audio", d_audio, in_stride, torch.int16 if fin == AUDIO_S16 else torch.float32),
+                     ("d_out", d_out, out_stride, torch.int16 if fout == AUDIO_S16 else torch.float32)]
+        for name, t, stride, dt in bufs:
+            if t is None or t.dtype != dt or not t.is_contiguous():
+                raise DDCError(-1, f"{name} must be a contiguous {dt} tensor")
+            need = (nch - 1) * stride + nsamp
+            if t.numel() < need:
+                raise DDCError(-1, f"{name} has {t.numel()} samples, need {need}")
+        for name, t, dt, cnt in sides:
+            if t is not None and (t.dtype != dt or not t.is_contiguous() or t.numel() < cnt):
+                raise DDCError(-1, f"{name} must be a contiguous {dt} tensor of at least {cnt} values")
+        check(self._L.sddc_ddc_channel_dcs_device(self._h, d_sense.data_ptr(), sense_stride,
+                                                  None if d_audio is None else d_audio.data_ptr(), nch, nsamp, in_stride,
+                                                  None if d_out is None else d_out.data_ptr(), out_stride,
+                                                  *(None if t is None else t.data_ptr() for _, t, _, _ in sides),
+                                                  _stream_handle(stream)))
 
 
 def _check_device_buffers(d_in, nblk, d_out, out_floats, fmt=0):

@@ -850,7 +850,8 @@ int sddc_ddc_channel_squelch_host(sddc_ddc_t *h, const void *audio, const void *
  * burst, a paging tone or a DTMF pair are the same question.  This stage is a bank of single-bin DFTs
  * (Goertzel filters) per channel over a real sense stream, a gate on the channel's audio that opens when
  * the strongest tone of the channel's mask holds enough of the window's energy, and side outputs that name
- * the tone and give every tone's power.  What it is NOT: no DCS (a digital code), no look-ahead (the gate of
+ * the tone and give every tone's power.  What it is NOT: no DCS (a digital code: that is the channel DCS
+ * decoder below), no look-ahead (the gate of
  * a window comes from the windows before it), and the window length bounds the decode time.
  *
  * The definition (normative; csrc/tone_math.h holds the operations, shared by both backends, float,
@@ -932,6 +933,95 @@ int sddc_ddc_channel_tone_device(sddc_ddc_t *h, const void *d_sense, size_t sens
 int sddc_ddc_channel_tone_host(sddc_ddc_t *h, const void *sense, size_t sense_stride, const void *audio, int nch, size_t nsamp,
                                size_t in_stride, void *out, size_t out_stride, int32_t *tone, uint32_t *open, uint32_t *count,
                                float *level, float *powers);
+
+/* ---- channel DCS decoder: streaming per-channel digital code squelch -----------------------------
+ * The tone detector tells CTCSS users apart.  The other half of selective calling on shared FM channels is
+ * DCS: a 23-bit Golay (23, 12) codeword sent over and over as NRZ at 134.4 bit/s below the audio.  This stage
+ * takes the sign of a real sense stream (the discriminator audio, low-passed and free of DC), sorts the signs
+ * of a window into eighths of a bit, forms the 23 bit sums at each of the 8 timing phases, keeps the phase
+ * with the widest eye, matches its word against a table of codewords over all 23 rotations, and gates the
+ * channel's audio on the match.  What it is NOT: it does not detect the 134.4 Hz turn-off code (the eye
+ * collapses and the hang decides); it has no DC removal (the caller high-passes or DC-blocks and low-passes
+ * the discriminator audio, as for CTCSS); it does not track the bit clock across windows; the window bounds
+ * the decode time.
+ *
+ * The definition (normative; csrc/dcs_math.h holds the operations, shared by both backends, integer-only
+ * apart from the sign test).  B = SDDC_DDC_DCS_BLOCK = 256; p >= 0 is the stream index since the last set or
+ * reset, k = p div B its block, j = k div W its window, n = p - 256 W j the window-local index.
+ *   Per handle.  A bit phase word w in 2^-32 cycles per sample, 1 <= w <= 2^29 (a bit is at least 8 samples,
+ *                an eighth of it at least one); a window of W blocks (1..256) with 256 W w >= 24 * 2^32 (23
+ *                bits and a bit of timing slack); a table of ncodes (1..128) 23-bit codewords, bit 0 the first
+ *                on the air; error limits 0 <= e_open <= e_close <= 3; an attack of A windows (1..255); a hang of
+ *                H windows (0..65535); the formats of the sense stream, the audio and the output.
+ *   Per channel. Three int32: code, an index into the table, or SDDC_DDC_DCS_ANY = -1 (match the whole table:
+ *                scan), or SDDC_DDC_DCS_OFF = -2 (bypass: always open, the audio passes, the reported code is
+ *                -1); invert, 0 or 1 (1: the received word is complemented before matching); eye, 0..256.
+ *   Sense.       Real, SDDC_DDC_AUDIO_F32 or _S16.  s = +1 if x > 0, -1 if x < 0, else 0 (a NaN is 0).
+ *   Sub-bins.    m(n) = (w n) >> 29, the product in 64 bits.  S[m] = the sum of s over the window's samples
+ *                with that m, m = 0..191 (samples with m >= 192 do not count).
+ *   Phases.      t = 0..7: c[t][b] = S[8 b + t] + .. + S[8 b + t + 7], b = 0..22, which is the sum of s over
+ *                floor((w n - t 2^29) / 2^32) = b.  Q[t] = the sum over b of |c[t][b]|.  N[t] = the number of n <
+ *                256 W with t <= m(n) < t + 184, a set-time constant.  The best phase: the largest Q, the
+ *                lowest t on a tie.  The word: bit b = (c[t][b] > 0), complemented in 23 bits if invert.
+ *   Match.       d(i) = the minimum over r = 0..22 of popcount(word xor rot_r(cw_i)), rotating in 23 bits.
+ *                Over the channel's candidates (the one code, or the whole table) the best is the lowest d,
+ *                then the lowest i; a channel without candidates (OFF) has d = 24.  good = 256 Q[t] >= eye N[t];
+ *                u = good && d <= e_open; v = good && d <= e_close.
+ *   Gate.        The squelch's state machine, once per completed window, exactly as in the tone detector: r = u
+ *                ? min(r + 1, A) : 0; n = v ? 0 : min(n + 1, H + 1); open = open ? (n <= H) : (r >= A); all zero
+ *                on a new stream.  The gate after window j applies to window j + 1.
+ *   Audio.       Optional (d_audio NULL: detect only), F32 or S16 in and out.  A sample of an open window
+ *                passes bit for bit, a closed one is +0; the conversions are the tone detector's.
+ *   Side outputs, each NULL or per channel: code (int32): the best index of the last completed window if v
+ *                held there, else -1; open (uint32) and count (uint32): as in the tone detector; info ([nch][4]
+ *                uint32): Q, N, d and t of the last completed window, the figures to calibrate eye from (256 Q
+ *                / N is the eye in the unit of `eye`).  Before any window completes: -1, 0 (bypass: 1), zeros.
+ * Everything is bit-identical from run to run, for any cut of a stream into calls, stream, grid and run
+ * length, for a channel alone or among others, and between a GPU handle and a CPU handle, with no condition
+ * on the sample magnitudes: after the sign test every value is an integer and every sum is order-free.
+ * State per handle, on the device for a GPU handle, independent of every other stage's: the position; per
+ * channel the gate, the last completed window's results and the unfinished window's 192 sub-bin sums. */
+#define SDDC_DDC_DCS_BLOCK 256
+#define SDDC_DDC_DCS_MAX_CODES 128
+#define SDDC_DDC_DCS_MAX_WINDOW 256
+#define SDDC_DDC_DCS_MAX_WORD (1u << 29)
+#define SDDC_DDC_DCS_MAX_ERRORS 3
+#define SDDC_DDC_DCS_MAX_EYE 256
+#define SDDC_DDC_DCS_MAX_ATTACK 255
+#define SDDC_DDC_DCS_MAX_HANG 65535
+#define SDDC_DDC_DCS_ANY (-1)
+#define SDDC_DDC_DCS_OFF (-2)
+/* The 23-bit codeword of the DCS code `code` = 0..511 (its three octal digits): d = 0x800 | code, parity = (d
+ * x^11) mod g over GF(2) with g = 0xC75 (x^11 + x^10 + x^6 + x^5 + x^4 + x^2 + 1), cw = parity << 12 | d; 023
+ * (octal) gives 0x763813.  SDDC_ERR_ARG: code outside 0..511 or cw NULL.  Stateless. */
+int sddc_ddc_dcs_codeword(int code, uint32_t *cw);
+/* word = round(bitrate / fs * 2^32), blocks = ceil(24 * 2^32 / (256 word)): the phase word and the shortest
+ * window for it (134.4 bit/s: 6 blocks at 8 kS/s, 34 at 48 kS/s).  SDDC_ERR_ARG if word is 0 or above 2^29,
+ * blocks is above 256, an argument is not finite or not positive, or a pointer is NULL.  Stateless. */
+int sddc_ddc_dcs_window(double fs, double bitrate, uint32_t *word, int *blocks);
+/* codewords: host array [ncodes], each below 2^23; params: host array [nch][3] = (code, invert, eye); 1 <= nch
+ * <= SDDC_DDC_MAX_CHANNELS; word, window, e_open, e_close, attack, hang as above; the formats
+ * SDDC_DDC_AUDIO_F32 or _S16.  A violation returns SDDC_ERR_ARG and sets nothing.  codewords or params NULL
+ * or nch == 0 turns the stage off and frees its state.  Every set call zeroes the state and the position,
+ * and waits for the stage's launches in flight. */
+int sddc_ddc_set_channel_dcs_decoder(sddc_ddc_t *h, const uint32_t *codewords, int ncodes, const int32_t *params, int nch,
+                                     uint32_t word, int window, int e_open, int e_close, int attack, int hang, int sense_format,
+                                     int in_format, int out_format);
+/* zero the state and the position: the next call starts a closed stream (SDDC_ERR_STATE: no decoder set) */
+int sddc_ddc_channel_dcs_reset(sddc_ddc_t *h);
+/* GPU handles; enqueued on hip_stream, returns after launch.  The buffers, strides, alignment, overlap rules
+ * and errors of sddc_ddc_channel_tone_device.  d_code, d_open, d_count: NULL or nch device entries; d_info:
+ * NULL or [nch][4].  A failed call changes no state.  The calls of one handle share the state and the
+ * position: they run one after the other in call order, whatever their streams. */
+int sddc_ddc_channel_dcs_device(sddc_ddc_t *h, const void *d_sense, size_t sense_stride, const void *d_audio, int nch,
+                                size_t nsamp, size_t in_stride, void *d_out, size_t out_stride, int32_t *d_code, uint32_t *d_open,
+                                uint32_t *d_count, uint32_t *d_info, void *hip_stream);
+/* Host buffers, the same layouts.  GPU handle: copy in, kernels, copy back, synchronous; it advances the
+ * same device state as the device call.  CPU handle: the definition's loop through the same arithmetic
+ * header. */
+int sddc_ddc_channel_dcs_host(sddc_ddc_t *h, const void *sense, size_t sense_stride, const void *audio, int nch, size_t nsamp,
+                              size_t in_stride, void *out, size_t out_stride, int32_t *code, uint32_t *open, uint32_t *count,
+                              uint32_t *info);
 
 /* ---- ingest ---------------------------------------
  * Pin a caller-owned host region (hipHostRegister) so the host path DMAs blocks
