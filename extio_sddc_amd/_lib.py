@@ -78,6 +78,12 @@ SIGNATURES = {
     "sddc_ddc_channel_demodulate_device": (_I, [_P, _P, _I, _SZ, _SZ, _P, _SZ, _P, _P]),
     "sddc_ddc_channel_demodulate_host": (_I, [_P, _P, _I, _SZ, _SZ, _P, _SZ, _P]),
     "sddc_ddc_biquad": (_I, [_I, ctypes.c_double, ctypes.c_double, _P]),
+    "sddc_ddc_set_channel_audio_resampler": (_I, [_P, _P, _I, _I, _I, _I, _I, _I]),
+    "sddc_ddc_channel_audio_resampler_formats": (_I, [_P, _I, _I]),
+    "sddc_ddc_channel_audio_resampler_reset": (_I, [_P]),
+    "sddc_ddc_channel_audio_resample_samples": (_SZ, [_P, _SZ]),
+    "sddc_ddc_channel_audio_resample_device": (_I, [_P, _P, _I, _SZ, _SZ, _P, _SZ, _P, _P]),
+    "sddc_ddc_channel_audio_resample_host": (_I, [_P, _P, _I, _SZ, _SZ, _P, _SZ, _P]),
     "sddc_ddc_set_channel_audio_filter": (_I, [_P, _P, _I, _I, _I, _I]),
     "sddc_ddc_channel_audio_filter_reset": (_I, [_P]),
     "sddc_ddc_channel_audio_filter_device": (_I, [_P, _P, _I, _SZ, _SZ, _P, _SZ, _P]),

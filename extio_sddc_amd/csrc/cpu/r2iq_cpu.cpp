@@ -457,6 +457,48 @@ void R2iq::channel_resample(const void *iq, bool cs16, float inv_s, int nch, siz
     }
 }
 
+// The channel audio resampler: per channel the stream [tail | the call's sample values] as floats, and
+// per output audio_resample_math.h's ars_dot on its phase's taps g[p][.] and its newest sample: scalar
+// fmaf in the definition's four-sum order, the device kernel's sequence on the same floats.
+void R2iq::channel_audio_resample(const void *in, bool in16, int nch, size_t nsamp, size_t in_stride, const float *taps,
+                                  int ntaps, int L, int M, int e, size_t nout, float *tail, void *out, bool out16,
+                                  size_t out_stride)
+{
+    const int K = (ntaps + L - 1) / L;
+    const size_t H = (size_t)K - 1;
+    std::vector<float> g((size_t)L * (size_t)K), x(H + nsamp);
+    ars::ars_order_taps(taps, ntaps, L, g.data());
+    const uint64_t ds = (uint64_t)(M / L);
+    const int dp = M % L;
+    for (int c = 0; c < nch; c++) {
+        float *tl = tail + (size_t)c * H;
+        std::copy(tl, tl + H, x.begin());
+        if (in16) {
+            const int16_t *v = static_cast<const int16_t *>(in) + (size_t)c * in_stride;
+            for (size_t i = 0; i < nsamp; i++) x[H + i] = ars::ars_value(v[i]);
+        } else {
+            const float *v = static_cast<const float *>(in) + (size_t)c * in_stride;
+            std::copy(v, v + nsamp, x.begin() + (ptrdiff_t)H);
+        }
+        float *yf = static_cast<float *>(out) + (size_t)c * out_stride;
+        int16_t *ys = static_cast<int16_t *>(out) + (size_t)c * out_stride;
+        uint64_t s = (uint64_t)e / (uint64_t)L;   // output k's sample and phase, stepped by M / L
+        int p = e % L;
+        for (size_t m = 0; m < nout; m++) {
+            const float y = ars::ars_dot(g.data() + (size_t)p * (size_t)K, x.data() + H + s, K);
+            if (out16) ys[m] = demod::demod_s16(y);
+            else yf[m] = y;
+            s += ds;
+            p += dp;
+            if (p >= L) {
+                p -= L;
+                s++;
+            }
+        }
+        std::copy(x.end() - (ptrdiff_t)H, x.end(), tl);
+    }
+}
+
 // The channel demodulator: demod_math.h's formulas sample by sample; the previous sample of the
 // call's first one is the kept value, and the call's last sample value is kept for the next call.
 void R2iq::channel_demodulate(const void *iq, bool cs16, float inv_s, int nch, size_t nsamp, size_t in_stride,

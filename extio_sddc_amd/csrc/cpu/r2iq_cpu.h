@@ -25,6 +25,7 @@
 
 #include "../agc_math.h"
 #include "../audio_iir_math.h"
+#include "../audio_resample_math.h"
 #include "../blanker_math.h"
 #include "../demod_math.h"
 #include "../squelch_math.h"
@@ -89,6 +90,15 @@ public:
     static void channel_resample(const void *iq, bool cs16, float inv_s, int nch, size_t nsamp, size_t in_stride,
                                  const float *taps, int ntaps, int L, int M, int e, size_t nout, float *tail, float *out,
                                  size_t out_stride);
+    // The channel audio resampler (sddc_ddc.h, sddc_ddc_channel_audio_resample_host;
+    // audio_resample_math.h): the resampler's outputs on nch REAL streams (float, or int16 read as
+    // (float)v when in16, channel c at in + c * in_stride samples), each the definition's fixed
+    // sequence of fmaf, the device kernel's.  tail: [nch][K - 1] floats, each channel's last sample
+    // values before the call, replaced by those after it.  Outputs float, or int16 (demod_s16) when
+    // out16, at out + c * out_stride samples.  Stateless otherwise.
+    static void channel_audio_resample(const void *in, bool in16, int nch, size_t nsamp, size_t in_stride,
+                                       const float *taps, int ntaps, int L, int M, int e, size_t nout, float *tail,
+                                       void *out, bool out16, size_t out_stride);
     // The channel demodulator (sddc_ddc.h, sddc_ddc_channel_demodulate_host; demod_math.h): channel c's
     // nsamp samples demodulated by chan[c] (mode, gain, BFO word) at stream position pos, streams and
     // formats as for channel_decimate; channel c's outputs (float, or int16 when s16) at out + c *

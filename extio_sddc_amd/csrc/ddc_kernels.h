@@ -249,6 +249,42 @@ hipError_t launch_channel_resample(const KernelTables &t, const void *d_iq, int 
                                    int e, size_t nout, const float2 *d_tail_in, float2 *d_tail_out, float *d_out,
                                    size_t out_stride, int max_wgs, int device, hipStream_t s);
 
+// Channel audio resampler (ddc_channel_audio_resample.hip, sddc_ddc_channel_audio_resample_device): the
+// resampler's sum (audio_resample_math.h: the same fixed order on both backends) on nch REAL streams,
+// float (in_s16 = 0) or int16 read as (float)v, channel c at c * in_stride samples, aligned to one sample,
+// any nsamp >= 1; outputs float or int16 (demod_s16) at c * out_stride samples.  e, nout, d_taps as for the
+// resampler.  d_tail_in / d_tail_out: [nch][K - 1] floats (two buffers; both may be null when K == 1).
+// One work item per (channel, tile of ta values of a); a call without an output still moves the tails.
+// An LDS slot is one float, so a tile holds twice the resampler's samples; a short tile (small M) takes
+// the kernel instance with the small LDS, which doubles the workgroups per CU.  max_wgs > 0 caps the
+// grid (tests).  The caller has checked the strides and the alignment of the bases to a sample.
+constexpr int kChArsLds = 16256;       // float slots of LDS per tile (+ 128 of slack: 64 KiB, 2 workgroups per CU)
+constexpr int kChArsLdsSmall = 8064;   // the small instance's (+ 128 of slack: 32 KiB, 5 workgroups per CU)
+constexpr int kChArsMaxA = 1024;       // values of a per tile at most (16 wave units per phase)
+constexpr int kChArsSmallMinA = 512;   // the small instance is taken when its tile holds this many a
+constexpr int kChArsPitchPad = 31;     // the pitch search's range above the columns needed
+static_assert((kChArsLds + 128) * 4 == 65536 && (kChArsLdsSmall + 128) * 4 == 32768, "LDS bytes per workgroup");
+static_assert(kChArsLds / kChResMaxDown - ((kChResMaxK - 2 + kChResMaxDown) / kChResMaxDown + 1) - 1 >= 1,
+              "a tile of both maxima holds an output");
+static_assert(kChArsLds + kChResMaxDown < 65536, "a tile's positions divide by M through a 16-bit magic");
+// The tile of (L, M, ntaps, input format): K, the values of a per tile, the LDS slots of the instance
+// taken (kChArsLds or kChArsLdsSmall), the polyphase rows' pitch in float slots and the modelled extra
+// LDS cycles of the stage's stores per wave (channel_audio_resample_pitch).
+struct ChArsLayout {
+    int K = 0, ta = 0, lds = 0, pitch = 0, store_conflicts = 0;
+};
+ChArsLayout channel_audio_resample_layout(int L, int M, int ntaps, int in_s16);
+// The pitch in [need, max_pitch] of a transposition by `mod` into 4-byte slots whose stores cost the
+// fewest extra LDS cycles, the smallest of equals: lane l of a 32-lane half holds samples V l + e (V = 4
+// floats or 8 int16 of a 16-byte load) and stores e with one ds_write_b32, banked on the slot mod 32; the
+// instruction's own 4 cycles hide a 2-way conflict in both halves (tools/channel_audio_resample_banks.py).
+// A model at offset 0: the kernel's vectors start pg - al positions into the tile, which shifts the rows.
+int channel_audio_resample_pitch(int mod, int need, int max_pitch, int V, int *store_conflicts);
+hipError_t launch_channel_audio_resample(const KernelTables &t, const void *d_in, int in_s16, int nch, size_t nsamp,
+                                         size_t in_stride, const float *d_taps, int ntaps, int L, int M, int e,
+                                         size_t nout, const float *d_tail_in, float *d_tail_out, void *d_out,
+                                         int out_s16, size_t out_stride, int max_wgs, int device, hipStream_t s);
+
 // Channel demodulator (ddc_channel_demod.hip, sddc_ddc_channel_demodulate_device): AM / FM / BFO audio
 // (demod_math.h) from nch streams laid out as for the decimator, any nsamp >= 1.  d_chan: [nch] mode,
 // gain and BFO word; pos: the stream position of the call's first sample mod 2^32.  d_last_in /

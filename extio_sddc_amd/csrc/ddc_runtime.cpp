@@ -793,6 +793,12 @@ struct sddc_ddc {
     ChannelStream chdec, chres;            // max_wgs: SDDC_DDC_PARAM_CH{DEC,RES}_MAX_WGS
     int chdec_R = 0;
     int chres_L = 0, chres_M = 0, chres_e = 0;
+    // channel audio resampler (sddc_ddc_channel_audio_resample_*): a ChannelStream whose tails hold
+    // REAL sample values, [nch][K - 1] floats at the start of its float2 buffers, which are sized
+    // ceil((K - 1) / 2) float2 per channel; d_out holds output samples of either format.  The
+    // position is reduced as the resampler's (audio_resample_math.h).
+    ChannelStream chars;                   // max_wgs: SDDC_DDC_PARAM_CHARS_MAX_WGS
+    int chars_L = 0, chars_M = 0, chars_e = 0, chars_in_fmt = 0, chars_out_fmt = 0;
     ChannelDemod chdem;                    // max_wgs: SDDC_DDC_PARAM_CHDEM_MAX_WGS
     ChannelAudio chaud;
     ChannelAgc chagc;
@@ -1151,6 +1157,7 @@ int sddc_ddc_destroy(sddc_ddc_t *h)
         (void)h->chsp_readers.sync();
         (void)h->chdec.readers.sync();
         (void)h->chres.readers.sync();
+        (void)h->chars.readers.sync();
         (void)h->chdem.readers.sync();
         (void)h->chaud.readers.sync();
         (void)h->chagc.readers.sync();
@@ -1191,6 +1198,7 @@ int sddc_ddc_destroy(sddc_ddc_t *h)
         h->chsp_readers.clear();
         h->chdec.free_all();
         h->chres.free_all();
+        h->chars.free_all();
         h->chdem.free_all();
         h->chaud.free_all();
         h->chagc.free_all();
@@ -1784,6 +1792,10 @@ int sddc_ddc_internal_set_param(sddc_ddc_t *h, int param, int value)
     case SDDC_DDC_PARAM_CHDCS_BALLOT:
         if (value != 0 && value != 1) return fail(SDDC_ERR_ARG, "channel DCS decoder ballot route %d is not 0 or 1", value);
         h->chdcs.ballot = value;
+        return SDDC_OK;
+    case SDDC_DDC_PARAM_CHARS_MAX_WGS:
+        if (value < 0) return fail(SDDC_ERR_ARG, "channel audio resampler workgroup cap %d is negative", value);
+        h->chars.max_wgs = value;
         return SDDC_OK;
     default:
         return fail(SDDC_ERR_ARG, "unknown parameter %d", param);
@@ -2610,6 +2622,203 @@ int sddc_ddc_channel_resample_host(sddc_ddc_t *h, const void *iq, int nch, size_
                                               return chres_launch(h, d_in, nch, nsamp, in_stride, d_out, out_stride, nout,
                                                                   h->stream);
                                           });
+    if (rc == SDDC_OK && nout_p) *nout_p = nout;
+    return rc;
+}
+
+/* ---- channel audio resampler: a streaming rational L/M polyphase FIR on real audio ---------- */
+/* internal (sddc_ddc_internal.h): the kernel's tile of (up, down, ntaps, input format) */
+int sddc_ddc_internal_chars_layout(int up, int down, int ntaps, int in_s16, int *tile_a, int *lds, int *pitch,
+                                   int *store_conflicts)
+{
+    if (!chres_factors_ok(up, down) || ntaps < 1 || ntaps > SDDC_DDC_RESAMPLE_MAX_TAPS ||
+        (ntaps + up - 1) / up > SDDC_DDC_RESAMPLE_MAX_PHASE_TAPS || !tile_a || !lds || !pitch || !store_conflicts)
+        return fail(SDDC_ERR_ARG, "chars layout: up %d, down %d, ntaps %d or a null pointer", up, down, ntaps);
+    const sddc::ChArsLayout g = sddc::channel_audio_resample_layout(up, down, ntaps, in_s16);
+    *tile_a = g.ta;
+    *lds = g.lds;
+    *pitch = g.pitch;
+    *store_conflicts = g.store_conflicts;
+    return SDDC_OK;
+}
+
+/* internal: the pitch search alone (tools/channel_audio_resample_banks.py) */
+int sddc_ddc_internal_chars_pitch(int mod, int need, int max_pitch, int V, int *store_conflicts)
+{
+    if (mod < 1 || need < 1 || max_pitch < need || (V != 4 && V != 8) || !store_conflicts)
+        return fail(SDDC_ERR_ARG, "chars pitch: mod %d, need %d, max %d, V %d or a null pointer", mod, need, max_pitch, V);
+    return sddc::channel_audio_resample_pitch(mod, need, max_pitch, V, store_conflicts);
+}
+
+/* internal: the stream position, the tails left as they are */
+int sddc_ddc_internal_chars_set_position(sddc_ddc_t *h, uint64_t pos)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->chars.taps.empty()) return fail(SDDC_ERR_STATE, "chars set position: no audio resampler set");
+    h->chars_e = sddc::ars::ars_position(h->chars_L, h->chars_M, pos);   // host state: a launch in flight has its own copy
+    return SDDC_OK;
+}
+
+int sddc_ddc_set_channel_audio_resampler(sddc_ddc_t *h, const float *taps, int ntaps, int up, int down, int nch,
+                                         int in_format, int out_format)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    const bool off = !taps || ntaps == 0;
+    int K = 0;
+    float ordered[SDDC_DDC_RESAMPLE_MAX_TAPS + SDDC_DDC_RESAMPLE_MAX_UP];   // the kernel's order: up K < ntaps + up
+    if (!off) {
+        if (ntaps < 1 || ntaps > SDDC_DDC_RESAMPLE_MAX_TAPS)
+            return fail(SDDC_ERR_ARG, "channel audio resampler: ntaps %d outside 1..%d", ntaps, SDDC_DDC_RESAMPLE_MAX_TAPS);
+        if (!chres_factors_ok(up, down))
+            return fail(SDDC_ERR_ARG, "channel audio resampler: up %d (1..%d) and down %d (1..%d) must be coprime and not both 1",
+                        up, SDDC_DDC_RESAMPLE_MAX_UP, down, SDDC_DDC_RESAMPLE_MAX_DOWN);
+        K = (ntaps + up - 1) / up;
+        if (K > SDDC_DDC_RESAMPLE_MAX_PHASE_TAPS)
+            return fail(SDDC_ERR_ARG, "channel audio resampler: ceil(ntaps / up) = %d is above %d", K,
+                        SDDC_DDC_RESAMPLE_MAX_PHASE_TAPS);
+        if (nch < 1 || nch > SDDC_DDC_MAX_CHANNELS)
+            return fail(SDDC_ERR_ARG, "channel audio resampler: nch %d outside 1..%d", nch, SDDC_DDC_MAX_CHANNELS);
+        for (int fmt : {in_format, out_format})
+            if (fmt != SDDC_DDC_AUDIO_F32 && fmt != SDDC_DDC_AUDIO_S16)
+                return fail(SDDC_ERR_ARG, "channel audio resampler: unknown sample format %d", fmt);
+        for (int j = 0; j < ntaps; j++)
+            if (!std::isfinite(taps[j])) return fail(SDDC_ERR_ARG, "channel audio resampler: tap %d is not finite", j);
+        sddc::ars::ars_order_taps(taps, ntaps, up, ordered);
+    }
+    std::lock_guard<std::mutex> lk(h->mu);
+    // K - 1 floats per channel in ceil((K - 1) / 2) float2
+    if (int rc = h->chars.configure(h, "channel audio resampler", taps, ntaps, ordered, (size_t)up * (size_t)K, K / 2, nch))
+        return rc;
+    h->chars_L = off ? 0 : up;
+    h->chars_M = off ? 0 : down;
+    h->chars_e = 0;
+    h->chars_in_fmt = off ? 0 : in_format;
+    h->chars_out_fmt = off ? 0 : out_format;
+    return SDDC_OK;
+}
+
+int sddc_ddc_channel_audio_resampler_formats(sddc_ddc_t *h, int in_format, int out_format)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    for (int fmt : {in_format, out_format})
+        if (fmt != SDDC_DDC_AUDIO_F32 && fmt != SDDC_DDC_AUDIO_S16)
+            return fail(SDDC_ERR_ARG, "channel audio resampler: unknown sample format %d", fmt);
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->chars.taps.empty()) return fail(SDDC_ERR_STATE, "channel audio resampler formats: no audio resampler set");
+    h->chars_in_fmt = in_format;   // host state: a launch in flight has its own copy
+    h->chars_out_fmt = out_format;
+    return SDDC_OK;
+}
+
+int sddc_ddc_channel_audio_resampler_reset(sddc_ddc_t *h)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->chars.taps.empty()) return fail(SDDC_ERR_STATE, "channel audio resampler reset: no audio resampler set");
+    if (int rc = h->chars.reset(h)) return rc;
+    h->chars_e = 0;
+    return SDDC_OK;
+}
+
+size_t sddc_ddc_channel_audio_resample_samples(sddc_ddc_t *h, size_t nsamp)
+{
+    if (!h) return 0;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->chars.taps.empty() || nsamp > ((size_t)1 << 40)) return 0;
+    return (size_t)sddc::ars::ars_count(h->chars_L, h->chars_M, h->chars_e, nsamp);
+}
+
+// the checks both calls share (under h->mu: the formats, the resampler and the position are read here)
+static int check_chars_args(const sddc_ddc_t *h, const void *in, int nch, size_t nsamp, size_t in_stride, const void *out,
+                            size_t out_stride, size_t *nout)
+{
+    if (h->chars.taps.empty()) return fail(SDDC_ERR_STATE, "channel audio resample: no audio resampler set");
+    if (nch != h->chars.nch)
+        return fail(SDDC_ERR_STATE, "channel audio resample: the resampler is set for %d channels, the call has %d",
+                    h->chars.nch, nch);
+    if (nsamp == 0 || nsamp > ((size_t)1 << 40)) return fail(SDDC_ERR_ARG, "nsamp must be in 1..2^40 (got %zu)", nsamp);
+    *nout = (size_t)sddc::ars::ars_count(h->chars_L, h->chars_M, h->chars_e, nsamp);
+    if (nch > 1 && in_stride < nsamp) return fail(SDDC_ERR_ARG, "in_stride must be >= nsamp (got %zu, nsamp %zu)", in_stride, nsamp);
+    if (nch > 1 && out_stride < *nout)
+        return fail(SDDC_ERR_ARG, "out_stride must be >= nout (got %zu, nout %zu)", out_stride, *nout);
+    if (!in || !out) return fail(SDDC_ERR_ARG, "null buffer");
+    const uintptr_t is = h->chars_in_fmt == SDDC_DDC_AUDIO_S16 ? 2 : 4, os = h->chars_out_fmt == SDDC_DDC_AUDIO_S16 ? 2 : 4;
+    if (((uintptr_t)in & (is - 1)) != 0) return fail(SDDC_ERR_ARG, "the input must be %d-byte aligned", (int)is);
+    if (((uintptr_t)out & (os - 1)) != 0) return fail(SDDC_ERR_ARG, "the output must be %d-byte aligned", (int)os);
+    return SDDC_OK;
+}
+
+// the position advances once the launch is enqueued
+static int chars_launch(sddc_ddc_t *h, const void *d_in, int nch, size_t nsamp, size_t in_stride, void *d_out,
+                        size_t out_stride, size_t nout, hipStream_t s)
+{
+    return h->chars.launch(s, [&](const float2 *tail_in, float2 *tail_out) {
+        const hipError_t e = sddc::launch_channel_audio_resample(
+            h->tables, d_in, h->chars_in_fmt == SDDC_DDC_AUDIO_S16, nch, nsamp, in_stride, h->chars.d_taps,
+            (int)h->chars.taps.size(), h->chars_L, h->chars_M, h->chars_e, nout, reinterpret_cast<const float *>(tail_in),
+            reinterpret_cast<float *>(tail_out), d_out, h->chars_out_fmt == SDDC_DDC_AUDIO_S16, out_stride, h->chars.max_wgs,
+            h->device, s);
+        if (e == hipSuccess) h->chars_e = sddc::ars::ars_advance(h->chars_L, h->chars_M, h->chars_e, nsamp, nout);
+        return e;
+    });
+}
+
+int sddc_ddc_channel_audio_resample_device(sddc_ddc_t *h, const void *d_in, int nch, size_t nsamp, size_t in_stride,
+                                           void *d_out, size_t out_stride, size_t *nout, void *hip_stream)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(h->mu);   // the call reads the formats and the resampler: one consistent set
+    if (h->cpu) return fail(SDDC_ERR_STATE, "channel_audio_resample_device: a CPU handle has no device path");
+    size_t n = 0;
+    if (int rc = check_chars_args(h, d_in, nch, nsamp, in_stride, d_out, out_stride, &n)) return rc;
+    DeviceGuard g(h->device);
+    HIP_TRY(g.err);
+    if (int rc = chars_launch(h, d_in, nch, nsamp, in_stride, d_out, out_stride, n, (hipStream_t)hip_stream)) return rc;
+    if (nout) *nout = n;
+    return SDDC_OK;
+}
+
+int sddc_ddc_channel_audio_resample_host(sddc_ddc_t *h, const void *in, int nch, size_t nsamp, size_t in_stride, void *out,
+                                         size_t out_stride, size_t *nout_p)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    size_t nout = 0;
+    if (int rc = check_chars_args(h, in, nch, nsamp, in_stride, out, out_stride, &nout)) return rc;
+    ChannelStream &st = h->chars;
+    const bool in16 = h->chars_in_fmt == SDDC_DDC_AUDIO_S16, out16 = h->chars_out_fmt == SDDC_DDC_AUDIO_S16;
+    if (h->cpu) {
+        try {
+            sddc::cpu::R2iq::channel_audio_resample(in, in16, nch, nsamp, nch > 1 ? in_stride : 0, st.taps.data(),
+                                                    (int)st.taps.size(), h->chars_L, h->chars_M, h->chars_e, nout,
+                                                    st.tail_h.data(), out, out16, nch > 1 ? out_stride : 0);
+        } catch (const std::exception &ex) {   // thrown before any output or tail is written
+            return fail(SDDC_ERR_NOMEM, "cpu backend: %s", ex.what());
+        }
+        h->chars_e = sddc::ars::ars_advance(h->chars_L, h->chars_M, h->chars_e, nsamp, nout);
+        if (nout_p) *nout_p = nout;
+        return SDDC_OK;
+    }
+    DeviceGuard g(h->device);
+    HIP_TRY(g.err);
+    // the spans that hold every channel's samples and outputs (one float at least: a call without an output)
+    const size_t is = in16 ? 2 : 4, os = out16 ? 2 : 4;
+    const size_t in_bytes = ((size_t)(nch - 1) * (nch > 1 ? in_stride : 0) + nsamp) * is;
+    const size_t out_bytes = ((size_t)(nch - 1) * (nch > 1 ? out_stride : 0) + nout) * os;
+    if (int rc = grow_device_buffer(&st.d_in, &st.in_cap, in_bytes, "channel_audio_resample_host", "input bytes")) return rc;
+    if (int rc = grow_device_buffer(&st.d_out, &st.out_cap, out_bytes / 4 + 1, "channel_audio_resample_host", "output floats"))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(st.d_in, in, in_bytes, hipMemcpyHostToDevice, h->stream));
+    const int rc = chars_launch(h, st.d_in, nch, nsamp, in_stride, st.d_out, out_stride, nout, h->stream);
+    if (rc == SDDC_OK && nout) {   // the streams alone: the caller's memory between them stays as it is
+        if (nch == 1 || out_stride == nout)
+            HIP_TRY(hipMemcpyAsync(out, st.d_out, out_bytes, hipMemcpyDeviceToHost, h->stream));
+        else
+            HIP_TRY(hipMemcpy2DAsync(out, out_stride * os, st.d_out, out_stride * os, nout * os, (size_t)nch,
+                                     hipMemcpyDeviceToHost, h->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(h->stream));   // also after a failed launch: the caller's input is free again
     if (rc == SDDC_OK && nout_p) *nout_p = nout;
     return rc;
 }

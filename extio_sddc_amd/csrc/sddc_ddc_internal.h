@@ -140,6 +140,11 @@ extern "C" {
  * measured.  Both are sums of the same integers: the route changes no output bit and no side output (tests). */
 #define SDDC_DDC_PARAM_CHDCS_BALLOT 29
 
+/* SDDC_DDC_PARAM_CHARS_MAX_WGS = n > 0: the channel audio resampler kernel's grid is at most n
+ * workgroups, as param 14 for the resampler; 0 (default): one workgroup per item, or full residency
+ * with a loop.  The grid changes no output bit (tests). */
+#define SDDC_DDC_PARAM_CHARS_MAX_WGS 30
+
 int sddc_ddc_internal_set_param(sddc_ddc_t *h, int param, int value);
 /* Move the channel tone detector's stream position to pos, a multiple of 256 W (SDDC_ERR_ARG otherwise;
  * SDDC_ERR_STATE: no detector set): the unfinished window's sums and the unfinished block are cleared, the
@@ -166,6 +171,19 @@ int sddc_ddc_internal_chres_layout(int up, int down, int ntaps, int cs16, int *t
 /* Set the resampler's stream position to pos samples consumed (any value: it is kept reduced), the
  * tails left as they are: tests start a stream far out.  SDDC_ERR_STATE: no resampler set. */
 int sddc_ddc_internal_chres_set_position(sddc_ddc_t *h, uint64_t pos);
+/* The channel audio resampler kernel's tile of (up, down, ntaps, input format): the tile's values of
+ * a (up x that many outputs, down x that many samples), the LDS float slots of the kernel instance
+ * taken, the polyphase rows' pitch in float slots, and the modelled extra LDS cycles of the stage's
+ * stores per wave (no handle, no device).  SDDC_ERR_ARG outside the ABI's ranges. */
+int sddc_ddc_internal_chars_layout(int up, int down, int ntaps, int in_s16, int *tile_a, int *lds, int *pitch,
+                                   int *store_conflicts);
+/* The pitch search of that layout alone: the pitch in [need, max_pitch] for a transposition by mod with
+ * V = 4 or 8 samples per lane, and its modelled extra cycles (tools/channel_audio_resample_banks.py is
+ * the numpy model it is checked against).  Returns the pitch, or SDDC_ERR_ARG. */
+int sddc_ddc_internal_chars_pitch(int mod, int need, int max_pitch, int V, int *store_conflicts);
+/* Set the audio resampler's stream position to pos samples consumed (any value: it is kept reduced),
+ * the tails left as they are: tests start a stream far out.  SDDC_ERR_STATE: no audio resampler set. */
+int sddc_ddc_internal_chars_set_position(sddc_ddc_t *h, uint64_t pos);
 /* Set the demodulator's stream position (the index that the BFO phase w * (p + i) counts from), the
  * last samples left as they are: tests start a stream next to the 2^32 wrap.  SDDC_ERR_STATE: no
  * demodulator set. */

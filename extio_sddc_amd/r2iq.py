@@ -271,6 +271,7 @@ class R2iq:
         self._resamp = None  # (ntaps, up, down, nch) of setChannelResampler
         self._demod = None   # (nch, out_format) of setChannelDemodulator
         self._audio = None   # (nch, in_format, out_format) of setChannelAudioFilter
+        self._aresamp = None  # (nch, in_format, out_format) of setChannelAudioResampler
         self._agc = None     # (nch, in_format, out_format) of setChannelAgc
         self._blanker = None  # (nch, format) of setChannelBlanker
         self._squelch = None  # (nch, sense, in_format, out_format) of setChannelSquelch
@@ -737,6 +738,94 @@ class R2iq:
                                                          None if d_power is None else d_power.data_ptr(),
                                                          _stream_handle(stream)))
 
+
+    # -- channel audio resampler ------------------------------------------------------
+    def setChannelAudioResampler(self, taps, up: int = 0, down: int = 0, nch: int = 0, in_format: int = AUDIO_F32,
+                                 out_format: int = AUDIO_F32) -> None:
+        """The streaming rational up / down polyphase FIR of channel_audio_resample on REAL audio
+        streams: taps, factors and nch as for setChannelResampler (no implied gain), in_format /
+        out_format AUDIO_F32 or AUDIO_S16 (S16 is read as float(v) and written rounded to nearest
+        even and clamped).  A GPU handle and a CPU handle produce the same bits.  Every call zeroes
+        the kept stream tails and the position.  None or no taps turns the stage off."""
+        if taps is None or len(taps) == 0:
+            check(self._L.sddc_ddc_set_channel_audio_resampler(self._h, None, 0, 0, 0, 0, 0, 0))
+            self._aresamp = None
+            return
+        t = np.ascontiguousarray(np.asarray(taps, np.float32).reshape(-1))
+        check(self._L.sddc_ddc_set_channel_audio_resampler(self._h, t.ctypes.data, t.size, int(up), int(down), int(nch),
+                                                           int(in_format), int(out_format)))
+        self._aresamp = (int(nch), int(in_format), int(out_format))
+
+    def setChannelAudioResamplerFormats(self, in_format: int, out_format: int) -> None:
+        """The formats of the next calls, the stream left as it is (the tails hold sample values)."""
+        if self._aresamp is None:
+            raise DDCError(-4, "no channel audio resampler set")
+        check(self._L.sddc_ddc_channel_audio_resampler_formats(self._h, int(in_format), int(out_format)))
+        self._aresamp = (self._aresamp[0], int(in_format), int(out_format))
+
+    def channel_audio_resampler_reset(self) -> None:
+        """Zero every channel's tail and the stream position: the next call starts a new stream."""
+        check(self._L.sddc_ddc_channel_audio_resampler_reset(self._h))
+
+    def channel_audio_resample_samples(self, nsamp: int) -> int:
+        """Outputs per channel that the NEXT channel_audio_resample call of nsamp samples produces
+        (it depends on the stream position; 0 is a legal count)."""
+        if self._aresamp is None or nsamp < 0:
+            return 0
+        return int(self._L.sddc_ddc_channel_audio_resample_samples(self._h, int(nsamp)))
+
+    def channel_audio_resample_host(self, x: np.ndarray) -> np.ndarray:
+        """The audio resampler on a host array: x is float32 (AUDIO_S16 in: int16) [nch, nsamp], any
+        nsamp >= 1; a single stream may drop the channel axis.  Returns float32 (AUDIO_S16 out: int16)
+        [nch, nout] (nout may be 0) and keeps each channel's last ceil(ntaps / up) - 1 sample values
+        and the position for the next call."""
+        if self._aresamp is None:
+            raise DDCError(-4, "no channel audio resampler set")
+        _, fin, fout = self._aresamp
+        x = np.asarray(x, np.int16 if fin == AUDIO_S16 else np.float32)
+        if x.ndim == 1:
+            x = x[None, :]
+        x = np.ascontiguousarray(x)
+        if x.ndim != 2 or x.shape[1] < 1:
+            raise DDCError(-1, "x must be [nch, nsamp] with nsamp >= 1")
+        nch, nsamp = x.shape
+        nout = self.channel_audio_resample_samples(nsamp)
+        out = np.empty((nch, max(nout, 1)), np.int16 if fout == AUDIO_S16 else np.float32)
+        got = ctypes.c_size_t(0)
+        check(self._L.sddc_ddc_channel_audio_resample_host(self._h, x.ctypes.data, nch, nsamp, nsamp, out.ctypes.data,
+                                                           max(nout, 1), ctypes.addressof(got)))
+        return out[:, :got.value]
+
+    def channel_audio_resample_device(self, d_in, nch: int, nsamp: int, in_stride: int, d_out, out_stride: int,
+                                      stream=None) -> int:
+        """The audio resampler on the buffer channel_demodulate_device (or any audio stage) wrote: d_in
+        is a float32 (AUDIO_S16 in: int16) device tensor, channel c's nsamp samples at c * in_stride;
+        d_out float32 (AUDIO_S16 out: int16), channel c's nout outputs at c * out_stride.  Returns
+        nout = channel_audio_resample_samples(nsamp) at the call (possibly 0).  Enqueued on `stream`
+        like process_device; the calls of one handle run in call order."""
+        import torch
+        if self._aresamp is None:
+            raise DDCError(-4, "no channel audio resampler set")
+        if nch < 1 or nsamp < 1:
+            raise DDCError(-1, "nch and nsamp must be >= 1")
+        if not (d_in.is_cuda and d_out.is_cuda):
+            raise DDCError(-1, "device path needs device tensors")
+        want = torch.int16 if self._aresamp[1] == AUDIO_S16 else torch.float32
+        want_out = torch.int16 if self._aresamp[2] == AUDIO_S16 else torch.float32
+        if d_in.dtype != want or d_out.dtype != want_out:
+            raise DDCError(-1, f"d_in must be {want} and d_out {want_out}")
+        if not (d_in.is_contiguous() and d_out.is_contiguous()):
+            raise DDCError(-1, "tensors must be contiguous")
+        nout = self.channel_audio_resample_samples(nsamp)
+        for name, t, stride, n in (("d_in", d_in, in_stride, nsamp), ("d_out", d_out, out_stride, nout)):
+            need = (nch - 1) * stride + n
+            if t.numel() < need:
+                raise DDCError(-1, f"{name} has {t.numel()} samples, need {need}")
+        got = ctypes.c_size_t(0)
+        check(self._L.sddc_ddc_channel_audio_resample_device(self._h, d_in.data_ptr(), nch, nsamp, in_stride,
+                                                             d_out.data_ptr(), out_stride, ctypes.addressof(got),
+                                                             _stream_handle(stream)))
+        return int(got.value)
 
     # -- channel audio filter -------------------------------------------------------
     def setChannelAudioFilter(self, coeffs, in_format: int = AUDIO_F32, out_format: int = AUDIO_F32) -> None:

@@ -60,7 +60,10 @@ extern "C" {
                                        still 3: + biquad, set_channel_audio_filter, channel_audio_filter_reset,
                                        channel_audio_filter_device, channel_audio_filter_host (new symbols only);
                                        still 3: + agc_decay, set_channel_agc, channel_agc_reset,
-                                       channel_agc_device, channel_agc_host (new symbols only) */
+                                       channel_agc_device, channel_agc_host (new symbols only);
+                                       still 3: + set_channel_audio_resampler, channel_audio_resampler_formats, channel_audio_resampler_reset,
+                                       channel_audio_resample_samples, channel_audio_resample_device,
+                                       channel_audio_resample_host (new symbols only) */
 
 #define SDDC_DDC_HALF_FFT   4096    /* halfFft               fft_mt_r2iq.h:18 */
 #define SDDC_DDC_FFTN       8192    /* FFTN_R_ADC            config.h:49 */
@@ -495,6 +498,64 @@ int sddc_ddc_channel_demodulate_device(sddc_ddc_t *h, const void *d_iq, int nch,
  * arithmetic header, sample by sample; its power is summed in sample order. */
 int sddc_ddc_channel_demodulate_host(sddc_ddc_t *h, const void *iq, int nch, size_t nsamp, size_t in_stride,
                                      void *out, size_t out_stride, float *power);
+
+/* ---- channel audio resampler: a streaming rational L/M polyphase FIR on real audio ----------
+ * The decimator and the resampler above change the rate of IQ; every stage from the demodulator on
+ * works on real audio and none of them could change its rate.  This one does: the 48 kS/s
+ * discriminator output of an NBFM channel to the 8 or 12 kS/s sense stream of the tone detector and
+ * the DCS decoder (1/6, 1/4), the 250 kS/s output of a WFM discriminator to 48 kS/s audio (24/125),
+ * 48 k to 8 k / 16 k S16 for a voice codec.  It is the channel resampler's sum on nch REAL streams:
+ * real prototype taps h[0..ntaps-1], L = up, M = down, the resampler's limits (1 <= L <= 32, 1 <= M
+ * <= 256, gcd = 1, not L = M = 1, ntaps <= 4096, K = ceil(ntaps / L) <= 1024), integer decimation is
+ * L = 1, and there is NO implied gain (a caller who wants unity gain designs h with DC gain L).
+ * Sample values: SDDC_DDC_AUDIO_F32 is read as stored, SDDC_DDC_AUDIO_S16 as (float)v, as the audio
+ * filter reads it; there is no cs16_scale.  Output m has m*M = s*L + p (0 <= p < L), x[i] = 0 for
+ * i < 0, and is the sequence
+ *     a[j mod 4] = fmaf(h[p + j*L], x[s - j], a[j mod 4])   for j = 0 .. K-1;   y = (a0 + a1) + (a2 + a3)
+ * (h[k] = 0 for k >= ntaps; csrc/audio_resample_math.h) on BOTH backends: unlike the IQ resampler, a
+ * CPU handle runs the device's order.  S16 output is rounded as the demodulator rounds it: nearest
+ * even, clamped to [-32768, 32767], NaN as 0.
+ * Outputs per call: the resampler's count, ceil((N0+nsamp)*L/M) - ceil(N0*L/M)
+ * (sddc_ddc_resample_count); 0 is legal, writes nothing and still advances the state; 1 <= nsamp <=
+ * 2^40.  State per handle, independent of the IQ resampler's (both may be set): each channel's last
+ * K-1 sample VALUES as float32 (on the device for a GPU handle, on the host for a CPU handle), and one
+ * stream position on the host, reduced modulo M.  Values are kept, not codes, so the input format may
+ * change between two calls of one stream (sddc_ddc_channel_audio_resampler_formats); a set call
+ * starts a new stream.
+ * Layout: the audio stages'.  Channel c starts c*in_stride input samples into the input and
+ * c*out_stride output samples into the output; for nch > 1 in_stride >= nsamp and out_stride >= nout,
+ * any parity.  The buffers are aligned to one sample of their format only (4 or 2 bytes).  Nothing is
+ * written between the streams or outside them.
+ * An output is BIT-IDENTICAL for any cut of the same samples into calls, at any position, for any
+ * grid, on any stream, for a channel alone or among others, and between a GPU handle and a CPU handle.
+ * Each F32 output is within gamma * sum_j |h[p + j*L]| |x[s - j]|, gamma = n u / (1 - n u), n = K + 1,
+ * u = 2^-24, of the exact sum; S16 output adds 1/2 and the clamp. */
+/* taps, ntaps, up, down, nch: as for sddc_ddc_set_channel_resampler; in_format, out_format:
+ * SDDC_DDC_AUDIO_*; a violation (also a tap that is not finite) returns SDDC_ERR_ARG.  NULL or ntaps
+ * == 0 turns the stage off and frees its state.  Every set call copies the taps, zeroes the tails and
+ * the position, and waits for this stage's launches in flight. */
+int sddc_ddc_set_channel_audio_resampler(sddc_ddc_t *h, const float *taps, int ntaps, int up, int down, int nch,
+                                         int in_format, int out_format);
+/* The formats of the NEXT calls, the stream left as it is: the tails hold sample values, not codes, so
+ * the input (and the output) format may change between two calls of one stream.  SDDC_ERR_ARG: an
+ * unknown format; SDDC_ERR_STATE: not set. */
+int sddc_ddc_channel_audio_resampler_formats(sddc_ddc_t *h, int in_format, int out_format);
+/* zero every channel's tail and the position: the next call starts a new stream (SDDC_ERR_STATE:
+ * not set) */
+int sddc_ddc_channel_audio_resampler_reset(sddc_ddc_t *h);
+/* what the handle's NEXT call of nsamp samples would produce per channel (0 also: not set) */
+size_t sddc_ddc_channel_audio_resample_samples(sddc_ddc_t *h, size_t nsamp);
+/* GPU handles; enqueued on hip_stream, returns after launch.  *nout (may be NULL) receives the
+ * call's outputs per channel; d_out needs room for them.  SDDC_ERR_STATE: not set, another nch than
+ * the set one, a CPU handle.  SDDC_ERR_ARG: nsamp == 0 or above 2^40, a bad stride or alignment, a null
+ * buffer.  A failed call changes no state.  The calls of one handle share the tails and the position:
+ * they run one after the other in call order, whatever their streams. */
+int sddc_ddc_channel_audio_resample_device(sddc_ddc_t *h, const void *d_in, int nch, size_t nsamp, size_t in_stride,
+                                           void *d_out, size_t out_stride, size_t *nout, void *hip_stream);
+/* Host buffers, the same layouts.  GPU handle: copy in, kernel, copy back, synchronous; it advances
+ * the same device tails and position as the device call.  CPU handle: the same sequence, the same bits. */
+int sddc_ddc_channel_audio_resample_host(sddc_ddc_t *h, const void *in, int nch, size_t nsamp, size_t in_stride,
+                                         void *out, size_t out_stride, size_t *nout);
 
 /* ---- channel audio filter: a streaming biquad cascade per channel on the device -----------
  * What stands between the demodulator and playable audio: DC blocking, de-emphasis, the 300 Hz
