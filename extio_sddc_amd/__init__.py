@@ -23,6 +23,7 @@ from .r2iq import (SQUELCH_BLOCK, SQUELCH_LEVEL, SQUELCH_MUTE, SQUELCH_NOISE, SQ
                    SQUELCH_SENSE_CS16, SQUELCH_SENSE_F32, SQUELCH_SENSE_S16, SQUELCH_SENSE_SELF, squelch_blocks)
 from .r2iq import CTCSS_TONES, TONE_BLOCK, tone_window, tone_word  # noqa: F401
 from .r2iq import DCS_ANY, DCS_BLOCK, DCS_CODES, DCS_OFF, dcs_codeword, dcs_window  # noqa: F401
+from .r2iq import STEREO_AUTO, STEREO_BLOCK, STEREO_MONO, stereo_pilot_word  # noqa: F401
 
 __all__ = ["R2iq", "DDCError", "DEVICE_CPU", "BACKEND_CPU", "BACKEND_HIP", "build", "load", "kaiser", "filter_taps", "filter_response",
            "channel_tuning", "device_count", "output_samples", "HALF_FFT", "BLOCK", "FRAMES", "NDEC", "OUT_BLOCK",
@@ -36,4 +37,4 @@ __all__ = ["R2iq", "DDCError", "DEVICE_CPU", "BACKEND_CPU", "BACKEND_HIP", "buil
            "SQUELCH_BLOCK", "SQUELCH_OFF", "SQUELCH_LEVEL", "SQUELCH_NOISE", "SQUELCH_MUTE", "SQUELCH_SENSE_SELF",
            "SQUELCH_SENSE_F32", "SQUELCH_SENSE_S16", "SQUELCH_SENSE_CF32", "SQUELCH_SENSE_CS16", "squelch_blocks",
            "TONE_BLOCK", "CTCSS_TONES", "tone_word", "tone_window", "DCS_BLOCK", "DCS_ANY", "DCS_OFF", "DCS_CODES",
-           "dcs_codeword", "dcs_window"]
+           "dcs_codeword", "dcs_window", "STEREO_BLOCK", "STEREO_MONO", "STEREO_AUTO", "stereo_pilot_word"]

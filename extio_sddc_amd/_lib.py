@@ -109,6 +109,11 @@ SIGNATURES = {
     "sddc_ddc_channel_tone_device": (_I, [_P, _P, _SZ, _P, _I, _SZ, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _P]),
     "sddc_ddc_channel_tone_host": (_I, [_P, _P, _SZ, _P, _I, _SZ, _SZ, _P, _SZ, _P, _P, _P, _P, _P]),
     "sddc_ddc_internal_chtone_set_position": (_I, [_P, ctypes.c_uint64]),
+    "sddc_ddc_set_channel_stereo_decoder": (_I, [_P, ctypes.c_uint32, _P, _P, _I, _I, _I, _I, _I, _I]),
+    "sddc_ddc_channel_stereo_reset": (_I, [_P]),
+    "sddc_ddc_channel_stereo_device": (_I, [_P, _P, _I, _SZ, _SZ, _P, _P, _SZ, _P, _P, _P, _P, _P]),
+    "sddc_ddc_channel_stereo_host": (_I, [_P, _P, _I, _SZ, _SZ, _P, _P, _SZ, _P, _P, _P, _P]),
+    "sddc_ddc_internal_chst_set_position": (_I, [_P, ctypes.c_uint64]),
     "sddc_ddc_dcs_codeword": (_I, [_I, _P]),
     "sddc_ddc_dcs_window": (_I, [ctypes.c_double, ctypes.c_double, _P, _P]),
     "sddc_ddc_set_channel_dcs_decoder": (_I, [_P, _P, _I, _P, _I, ctypes.c_uint32, _I, _I, _I, _I, _I, _I, _I, _I]),

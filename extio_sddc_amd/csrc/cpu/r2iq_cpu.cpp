@@ -898,5 +898,89 @@ void R2iq::channel_dcs(const void *sense, bool sense16, const void *audio, bool 
     }
 }
 
+// The channel stereo decoder: stereo_math.h's stream, sample by sample; a block's sums when it completes.
+void R2iq::channel_stereo(const void *in, bool in16, int nch, size_t nsamp, size_t in_stride, uint32_t word,
+                          const uint8_t *modes, const float *thr, int window, int attack, int hang, uint64_t pos,
+                          StereoChannel *state, void *left, void *right, bool out16, size_t out_stride,
+                          uint32_t *stereo_out, uint32_t *count, float *level, float *phase)
+{
+    using namespace stereo;
+    const int B = kStereoBlock;
+    const uint32_t w2 = word * 2u;
+    // the pilot's and the carrier's phasors of a block's samples: they depend on i alone
+    float pc[kStereoBlock], ps[kStereoBlock], tc[kStereoBlock], ts[kStereoBlock];
+    for (int i = 0; i < B; i++) {
+        tone::tone_phasor(word, (uint32_t)i, &pc[i], &ps[i]);
+        tone::tone_phasor(w2, (uint32_t)i, &tc[i], &ts[i]);
+    }
+    for (int c = 0; c < nch; c++) {
+        const float *xf = static_cast<const float *>(in) + (size_t)c * in_stride;
+        const int16_t *xs = static_cast<const int16_t *>(in) + (size_t)c * in_stride;
+        float *lf = static_cast<float *>(left) + (size_t)c * out_stride, *rf = static_cast<float *>(right) + (size_t)c * out_stride;
+        int16_t *ls = static_cast<int16_t *>(left) + (size_t)c * out_stride, *rs = static_cast<int16_t *>(right) + (size_t)c * out_stride;
+        const bool autom = modes[c] == kStereoAuto;
+        const float To = thr[4 * c], Tc = thr[4 * c + 1], Emin = thr[4 * c + 2], g2 = thr[4 * c + 3];
+        StereoChannel &st = state[c];
+        int b = (int)(pos % (uint64_t)B);
+        uint64_t k = pos / (uint64_t)B;   // the stream's block index
+        uint32_t cnt = 0;
+        bool have = false;                // rr, ri are block k's
+        float rr = 0.f, ri = 0.f;
+        for (size_t i = 0; i < nsamp; i++) {
+            const float x = in16 ? (float)xs[i] : xf[i];
+            const bool fin = blank::blank_finite(x * x);
+            st.x[b] = fin ? x : 0.f;
+            st.bad |= fin ? 0u : 1u;
+            if (autom && st.open) {
+                if (!have) stereo_block(st.qr, st.qi, w2, (uint32_t)(k * (uint64_t)B), &rr, &ri);
+                have = true;
+                float L, R;
+                stereo_lr(x, g2, stereo_sub(tc[b], ts[b], rr, ri), &L, &R);
+                if (out16) ls[i] = demod::demod_s16(L), rs[i] = demod::demod_s16(R);
+                else lf[i] = L, rf[i] = R;
+                cnt++;
+            } else if (out16) {
+                ls[i] = rs[i] = demod::demod_s16(x);
+            } else if (in16) {
+                lf[i] = rf[i] = x;
+            } else {
+                __builtin_memcpy(&lf[i], &xf[i], 4);   // the stored word: a NaN keeps its payload
+                __builtin_memcpy(&rf[i], &xf[i], 4);
+            }
+            if (++b < B) continue;
+            b = 0;
+            have = false;
+            float tmp[kStereoBlock];
+            for (int m = 0; m < B; m++) tmp[m] = st.x[m] * st.x[m];
+            st.E = st.E + blank::blank_tree(tmp);
+            for (int m = 0; m < B; m++) tmp[m] = st.x[m] * pc[m];
+            const float Ck = blank::blank_tree(tmp);
+            for (int m = 0; m < B; m++) tmp[m] = st.x[m] * ps[m];
+            const float Sk = blank::blank_tree(tmp);
+            float cr, sr, re, im;
+            tone::tone_phasor(word, (uint32_t)(k * (uint64_t)B), &cr, &sr);
+            tone::tone_rotate(Ck, Sk, cr, sr, &re, &im);
+            st.zr = st.zr + re;
+            st.zi = st.zi + im;
+            k++;
+            if (k % (uint64_t)window != 0) continue;
+            // the window is complete
+            const float P = blank::blank_power(st.zr, st.zi);
+            bool u, v;
+            tone::tone_flags(P, st.E, st.bad != 0, To, Tc, Emin, &u, &v);
+            if (v) stereo_phase(st.zr, st.zi, P, &st.qr, &st.qi);
+            squelch::squelch_step(u, v, (uint32_t)attack, (uint32_t)hang, &st.r, &st.n, &st.open);
+            st.plast = P;
+            st.elast = st.E;
+            st.zr = st.zi = st.E = 0.f;
+            st.bad = 0;
+        }
+        if (stereo_out) stereo_out[c] = autom ? st.open : 0u;
+        if (count) count[c] = cnt;
+        if (level) level[2 * c] = st.plast, level[2 * c + 1] = st.elast;
+        if (phase) phase[2 * c] = st.qr, phase[2 * c + 1] = st.qi;
+    }
+}
+
 }  // namespace cpu
 }  // namespace sddc

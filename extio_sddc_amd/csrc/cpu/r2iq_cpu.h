@@ -30,6 +30,7 @@
 #include "../demod_math.h"
 #include "../squelch_math.h"
 #include "../tone_math.h"
+#include "../stereo_math.h"
 #include "../dcs_math.h"
 #include "fft_avx2.hpp"
 
@@ -193,6 +194,24 @@ public:
                             uint32_t word, const uint32_t *counts, int window, int e_open, int e_close, int attack, int hang,
                             uint64_t pos, DcsChannel *state, void *out, bool out16, size_t out_stride, int32_t *code,
                             uint32_t *open, uint32_t *count, uint32_t *info);
+    // The channel stereo decoder (sddc_ddc.h, sddc_ddc_channel_stereo_host; stereo_math.h): the definition's
+    // loop, sample by sample.  Channel c's nsamp MPX samples (float, or int16 when in16) at in + c * in_stride,
+    // its outputs (float, or int16 when out16) at left + c * out_stride and right + c * out_stride.  word: the
+    // pilot's phase word; modes: [nch]; thr: [nch][4] = (To, Tc, Emin, g2), scaled; window: W; pos: the stream
+    // index of the call's first sample; state: [nch], before the call and replaced by the one after it;
+    // stereo, count: null or [nch]; level, phase: null or [nch][2].
+    struct StereoChannel {
+        uint32_t r = 0, n = 0, open = 0;   // the gate after the last completed window
+        float qr = 1.f, qi = 0.f;          // the carrier's phase in force
+        float plast = 0.f, elast = 0.f;    // P and E of the last completed window
+        float zr = 0.f, zi = 0.f, E = 0.f; // the unfinished window's sums, and whether it holds a non-finite q
+        uint32_t bad = 0, pad = 0;
+        float x[stereo::kStereoBlock] = {};   // the unfinished block's samples, non-finite ones as 0
+    };
+    static void channel_stereo(const void *in, bool in16, int nch, size_t nsamp, size_t in_stride, uint32_t word,
+                               const uint8_t *modes, const float *thr, int window, int attack, int hang, uint64_t pos,
+                               StereoChannel *state, void *left, void *right, bool out16, size_t out_stride,
+                               uint32_t *stereo_out, uint32_t *count, float *level, float *phase);
     // demod_math.h's routines on arrays (the accuracy sweeps of tests/test_channel_demod_cpu.py)
     static void demod_angle_n(const float *im, const float *re, size_t n, float *out);
     static void demod_sincos_n(const uint32_t *words, size_t n, float *c, float *s);

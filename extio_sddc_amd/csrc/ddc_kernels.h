@@ -386,6 +386,24 @@ hipError_t launch_channel_tone(const KernelTables &t, const void *d_sense, int s
                                size_t out_stride, int *d_tone, uint32_t *d_open, uint32_t *d_count, float *d_level,
                                float *d_powers, int accumulate, int max_wgs, int device, hipStream_t s);
 
+// Channel stereo decoder (ddc_channel_stereo.hip, sddc_ddc_channel_stereo_device): one launch set of the
+// pilot measurement, its gate and the matrix (stereo_math.h) over nch real MPX streams (F32 or S16) into
+// d_left and d_right (F32 or S16); strides in samples.  pos: the stream index of the first sample; nsamp at
+// most kStereoMaxLaunch.  word: the pilot's phase word; d_modes: [nch] words (kStereoMono / kStereoAuto);
+// d_thr: [nch][4] floats (To, Tc, Emin, g2); d_state_in / d_state_out: [nch][kStereoStateWords] words before
+// / after (two buffers); d_scratch: kStereoScratchWords(nch, blocks that hold a sample) words; d_stereo,
+// d_count: null or [nch]; d_level, d_phase: null or [nch][2]; accumulate: d_count holds earlier launches of
+// the same call and is added to.  Three launches on s; max_wgs > 0 caps their grids (tests).  The caller has
+// checked the strides and the alignment of the bases to a sample.
+constexpr int kStereoStateWords = 268;
+constexpr size_t kStereoMaxLaunch = (size_t)1 << 28;
+constexpr size_t kStereoScratchWords(size_t nch, size_t blocks) { return nch * (2 * blocks + 1) * 4; }
+hipError_t launch_channel_stereo(const KernelTables &t, const void *d_in, int in_s16, int nch, size_t nsamp, size_t in_stride,
+                                 uint64_t pos, uint32_t word, const uint32_t *d_modes, const float *d_thr, int window, int attack,
+                                 int hang, const uint32_t *d_state_in, uint32_t *d_state_out, uint32_t *d_scratch, void *d_left,
+                                 void *d_right, int out_s16, size_t out_stride, uint32_t *d_stereo, uint32_t *d_count,
+                                 float *d_level, float *d_phase, int accumulate, int max_wgs, int device, hipStream_t s);
+
 // Channel DCS decoder (ddc_channel_dcs.hip, sddc_ddc_channel_dcs_device): one launch set of the sign
 // sub-bins, the bit sums, the match and the gate (dcs_math.h) over nch real sense streams (F32 or S16) and,
 // where d_audio is not null, their audio streams (F32 or S16 in and out); strides in samples.  pos: the

@@ -625,6 +625,68 @@ struct ChannelDcs {
     }
 };
 
+// The state of the channel stereo decoder (sddc_ddc_channel_stereo_*; stereo_math.h): the modes [nch] and the
+// scaled parameters [nch][4] = (To, Tc, Emin, g2) (empty = off) with their device copies, the handle's pilot
+// word, window, attack, hang and formats, the stream position (host) and each channel's state as
+// [nch][kStereoStateWords] words in two device buffers that swap per launch set, as ChannelTone's do (init: a
+// new stream's, with q = (1, 0)); d_scratch holds kStereoScratchWords of a launch set, grown on demand.  A CPU
+// handle keeps the state in state_h.  d_in / d_out / d_side are the host call's device buffers.  All under the
+// handle's mu.
+struct ChannelStereo {
+    static constexpr int kDefaultRunBlocks = 4096;
+    std::vector<uint8_t> modes;
+    std::vector<float> thr;
+    std::vector<uint32_t> init;
+    uint32_t word = 0;
+    int nch = 0, window = 0, attack = 0, hang = 0, in_fmt = 0, out_fmt = 0;
+    uint64_t pos = 0;
+    uint32_t *d_modes = nullptr;
+    float *d_thr = nullptr;
+    uint32_t *d_state[2] = {};
+    int cur = 0;
+    uint32_t *d_scratch = nullptr;
+    size_t scratch_cap = 0;
+    std::vector<sddc::cpu::R2iq::StereoChannel> state_h;
+    Readers readers;
+    int max_wgs = 0, run_blocks = 0;   // SDDC_DDC_PARAM_CHST_MAX_WGS, _RUN_BLOCKS (0: kDefaultRunBlocks)
+    void *d_in = nullptr, *d_out = nullptr;   // d_out: the left streams, then the right ones
+    uint32_t *d_side = nullptr;               // [nch] stereo, [nch] count, [nch][2] level, [nch][2] phase
+    size_t in_cap = 0, out_cap = 0, side_cap = 0;   // bytes, bytes, words
+
+    size_t state_words() const { return (size_t)nch * sddc::kStereoStateWords; }
+    void clear()
+    {
+        modes.clear();
+        thr.clear();
+        init.clear();
+        word = 0;
+        nch = window = attack = hang = in_fmt = out_fmt = 0;
+        pos = 0;
+        state_h.clear();
+        if (d_modes) (void)hipFree(d_modes);
+        if (d_thr) (void)hipFree(d_thr);
+        d_modes = nullptr;
+        d_thr = nullptr;
+        for (uint32_t *&p : d_state) {
+            if (p) (void)hipFree(p);
+            p = nullptr;
+        }
+        cur = 0;
+    }
+    void free_all()
+    {
+        clear();
+        if (d_scratch) (void)hipFree(d_scratch);
+        if (d_in) (void)hipFree(d_in);
+        if (d_out) (void)hipFree(d_out);
+        if (d_side) (void)hipFree(d_side);
+        d_scratch = d_side = nullptr;
+        d_in = d_out = nullptr;
+        scratch_cap = in_cap = out_cap = side_cap = 0;
+        readers.clear();
+    }
+};
+
 }  // namespace
 
 struct sddc_ddc {
@@ -806,6 +868,7 @@ struct sddc_ddc {
     ChannelSquelch chsq;
     ChannelTone chtone;
     ChannelDcs chdcs;
+    ChannelStereo chst;
 
     // CPU handle (device SDDC_DDC_DEVICE_CPU): the AVX2 backend; no HIP object above exists
     std::unique_ptr<sddc::cpu::R2iq> cpu;
@@ -1165,6 +1228,7 @@ int sddc_ddc_destroy(sddc_ddc_t *h)
         (void)h->chsq.readers.sync();
         (void)h->chtone.readers.sync();
         (void)h->chdcs.readers.sync();
+        (void)h->chst.readers.sync();
         if (h->d_tables) (void)hipFree(h->d_tables);
         for (auto &sl : h->hs) {
             if (sl.d_in) (void)hipFree(sl.d_in);
@@ -1206,6 +1270,7 @@ int sddc_ddc_destroy(sddc_ddc_t *h)
         h->chsq.free_all();
         h->chtone.free_all();
         h->chdcs.free_all();
+        h->chst.free_all();
         if (h->fsa.h_ring) (void)hipHostFree(h->fsa.h_ring);   // its writers were waited for above
         h->readers.clear();
         h->ch_readers.clear();
@@ -1796,6 +1861,15 @@ int sddc_ddc_internal_set_param(sddc_ddc_t *h, int param, int value)
     case SDDC_DDC_PARAM_CHARS_MAX_WGS:
         if (value < 0) return fail(SDDC_ERR_ARG, "channel audio resampler workgroup cap %d is negative", value);
         h->chars.max_wgs = value;
+        return SDDC_OK;
+    case SDDC_DDC_PARAM_CHST_MAX_WGS:
+        if (value < 0) return fail(SDDC_ERR_ARG, "channel stereo decoder workgroup cap %d is negative", value);
+        h->chst.max_wgs = value;
+        return SDDC_OK;
+    case SDDC_DDC_PARAM_CHST_RUN_BLOCKS:
+        if (value < 0 || value > (1 << 20))
+            return fail(SDDC_ERR_ARG, "channel stereo decoder run length %d outside 0..2^20 blocks", value);
+        h->chst.run_blocks = value;
         return SDDC_OK;
     default:
         return fail(SDDC_ERR_ARG, "unknown parameter %d", param);
@@ -4659,6 +4733,293 @@ int sddc_ddc_channel_dcs_host(sddc_ddc_t *h, const void *sense, size_t sense_str
         if (open) HIP_TRY(hipMemcpyAsync(open, d_open, n * 4, hipMemcpyDeviceToHost, h->stream));
         if (count) HIP_TRY(hipMemcpyAsync(count, d_count, n * 4, hipMemcpyDeviceToHost, h->stream));
         if (info) HIP_TRY(hipMemcpyAsync(info, d_info, n * 16, hipMemcpyDeviceToHost, h->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(h->stream));   // also after a failed launch: the caller's input is free again
+    return rc;
+}
+
+/* ---- channel stereo decoder: streaming WFM stereo from the MPX -------------------------------------- */
+static_assert(SDDC_DDC_STEREO_BLOCK == sddc::stereo::kStereoBlock && SDDC_DDC_STEREO_MAX_WINDOW == sddc::stereo::kStereoMaxWindow &&
+                  SDDC_DDC_STEREO_MONO == sddc::stereo::kStereoMono && SDDC_DDC_STEREO_AUTO == sddc::stereo::kStereoAuto,
+              "the arithmetic header's constants are the ABI's");
+static_assert(sizeof(sddc::cpu::R2iq::StereoChannel) == (size_t)sddc::kStereoStateWords * 4, "the CPU state holds what the device's does");
+
+int sddc_ddc_set_channel_stereo_decoder(sddc_ddc_t *h, uint32_t pilot_word, const uint8_t *modes, const float *params, int nch,
+                                        int window, int attack, int hang, int in_format, int out_format)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    const bool off = !modes || !params || nch == 0;
+    std::vector<uint8_t> md;
+    std::vector<float> thr;
+    std::vector<uint32_t> mw, init;
+    if (!off) {
+        if (nch < 1 || nch > SDDC_DDC_MAX_CHANNELS)
+            return fail(SDDC_ERR_ARG, "channel stereo decoder: nch %d outside 1..%d", nch, SDDC_DDC_MAX_CHANNELS);
+        if (pilot_word == 0) return fail(SDDC_ERR_ARG, "channel stereo decoder: the pilot word is 0");
+        if (window < 1 || window > SDDC_DDC_STEREO_MAX_WINDOW)
+            return fail(SDDC_ERR_ARG, "channel stereo decoder: window %d outside 1..%d blocks", window, SDDC_DDC_STEREO_MAX_WINDOW);
+        if (attack < 1 || attack > SDDC_DDC_TONE_MAX_ATTACK)
+            return fail(SDDC_ERR_ARG, "channel stereo decoder: attack %d outside 1..%d windows", attack, SDDC_DDC_TONE_MAX_ATTACK);
+        if (hang < 0 || hang > SDDC_DDC_TONE_MAX_HANG)
+            return fail(SDDC_ERR_ARG, "channel stereo decoder: hang %d outside 0..%d windows", hang, SDDC_DDC_TONE_MAX_HANG);
+        for (int fmt : {in_format, out_format})
+            if (fmt != SDDC_DDC_AUDIO_F32 && fmt != SDDC_DDC_AUDIO_S16)
+                return fail(SDDC_ERR_ARG, "channel stereo decoder: unknown sample format %d", fmt);
+        try {
+            md.assign(modes, modes + nch);
+            mw.assign(modes, modes + nch);
+            thr.resize((size_t)nch * 4);
+            init.assign((size_t)nch * sddc::kStereoStateWords, 0u);
+        } catch (const std::exception &ex) {
+            return fail(SDDC_ERR_NOMEM, "channel stereo decoder: %s", ex.what());
+        }
+        const sddc::cpu::R2iq::StereoChannel fresh;
+        for (int c = 0; c < nch; c++) {
+            const float ro = params[4 * c], rc = params[4 * c + 1], em = params[4 * c + 2], g = params[4 * c + 3];
+            if (modes[c] != SDDC_DDC_STEREO_MONO && modes[c] != SDDC_DDC_STEREO_AUTO)
+                return fail(SDDC_ERR_ARG, "channel stereo decoder: unknown mode %d of channel %d", (int)modes[c], c);
+            if (!(ro > 0.f && ro <= 1.f) || !(rc > 0.f && rc <= 1.f))
+                return fail(SDDC_ERR_ARG, "channel stereo decoder: rho_open %g or rho_close %g of channel %d is outside (0, 1]",
+                            (double)ro, (double)rc, c);
+            if (!(rc <= ro))
+                return fail(SDDC_ERR_ARG, "channel stereo decoder: channel %d has rho_close %g above rho_open %g", c, (double)rc, (double)ro);
+            thr[4 * (size_t)c] = sddc::tone::tone_scale(ro, window);
+            thr[4 * (size_t)c + 1] = sddc::tone::tone_scale(rc, window);
+            thr[4 * (size_t)c + 2] = sddc::tone::tone_scale(em == 0.f ? 0.f : em, window);
+            thr[4 * (size_t)c + 3] = sddc::stereo::stereo_g2(g == 0.f ? 0.f : g);
+            if (!(em >= 0.f) || !std::isfinite(thr[4 * (size_t)c + 2]))
+                return fail(SDDC_ERR_ARG, "channel stereo decoder: e_min %g of channel %d is not a value >= 0 with a finite 256 W e_min",
+                            (double)em, c);
+            if (!(g >= 0.f) || !std::isfinite(thr[4 * (size_t)c + 3]))
+                return fail(SDDC_ERR_ARG, "channel stereo decoder: the gain %g of channel %d is not a value >= 0 with a finite 2 g",
+                            (double)g, c);
+            std::memcpy(&init[(size_t)c * sddc::kStereoStateWords], &fresh, sizeof fresh);
+        }
+    }
+    std::lock_guard<std::mutex> lk(h->mu);
+    ChannelStereo &st = h->chst;
+    if (h->cpu) {
+        st.clear();
+        if (off) return SDDC_OK;
+        try {
+            st.state_h.assign((size_t)nch, sddc::cpu::R2iq::StereoChannel());
+        } catch (const std::exception &ex) {
+            st.clear();
+            return fail(SDDC_ERR_NOMEM, "channel stereo decoder: %s", ex.what());
+        }
+    } else {
+        DeviceGuard g(h->device);
+        HIP_TRY(g.err);
+        HIP_TRY(st.readers.sync());   // earlier launches, on any stream, may still use the state
+        st.clear();                   // a failed upload leaves the stage off
+        if (off) return SDDC_OK;
+        hipError_t e = hipMalloc(&st.d_modes, mw.size() * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMalloc(&st.d_thr, thr.size() * sizeof(float));
+        for (uint32_t *&p : st.d_state)
+            if (e == hipSuccess) e = hipMalloc(&p, init.size() * sizeof(uint32_t));
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            st.clear();
+            return fail(SDDC_ERR_NOMEM, "channel stereo decoder: no device memory for %d channels", nch);
+        }
+        // synchronous copies from pageable memory: done when they return, so the first launch may be on any stream
+        e = hipMemcpy(st.d_modes, mw.data(), mw.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(st.d_thr, thr.data(), thr.size() * sizeof(float), hipMemcpyHostToDevice);
+        for (uint32_t *p : st.d_state)
+            if (e == hipSuccess) e = hipMemcpy(p, init.data(), init.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e != hipSuccess) {
+            st.clear();
+            HIP_TRY(e);
+        }
+    }
+    st.modes = std::move(md);
+    st.thr = std::move(thr);
+    st.init = std::move(init);
+    st.word = pilot_word;
+    st.nch = nch;
+    st.window = window;
+    st.attack = attack;
+    st.hang = hang;
+    st.in_fmt = in_format;
+    st.out_fmt = out_format;
+    st.pos = 0;
+    return SDDC_OK;
+}
+
+int sddc_ddc_channel_stereo_reset(sddc_ddc_t *h)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    ChannelStereo &st = h->chst;
+    if (st.modes.empty()) return fail(SDDC_ERR_STATE, "channel stereo reset: no decoder set");
+    if (h->cpu) {
+        std::fill(st.state_h.begin(), st.state_h.end(), sddc::cpu::R2iq::StereoChannel());
+    } else {
+        DeviceGuard g(h->device);
+        HIP_TRY(g.err);
+        HIP_TRY(st.readers.sync());   // earlier launches, on any stream, may still use the state
+        HIP_TRY(hipMemcpy(st.d_state[st.cur], st.init.data(), st.init.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipDeviceSynchronize());   // the next launch may be on any stream
+    }
+    st.pos = 0;
+    return SDDC_OK;
+}
+
+int sddc_ddc_internal_chst_set_position(sddc_ddc_t *h, uint64_t pos)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    ChannelStereo &st = h->chst;
+    if (st.modes.empty()) return fail(SDDC_ERR_STATE, "channel stereo position: no decoder set");
+    if (pos % ((uint64_t)SDDC_DDC_STEREO_BLOCK * (uint64_t)st.window) != 0)
+        return fail(SDDC_ERR_ARG, "channel stereo position: %llu is no multiple of 256 W = %d", (unsigned long long)pos,
+                    SDDC_DDC_STEREO_BLOCK * st.window);
+    if (h->cpu) {
+        for (auto &ch : st.state_h) {
+            ch.zr = ch.zi = ch.E = 0.f;
+            ch.bad = 0;
+            std::fill(std::begin(ch.x), std::end(ch.x), 0.f);
+        }
+    } else {
+        DeviceGuard g(h->device);
+        HIP_TRY(g.err);
+        HIP_TRY(st.readers.sync());
+        // words 7 .. 10 of every channel: Zr, Zi, E and the bad flag (the stored block is not read at a block's start)
+        HIP_TRY(hipMemset2DAsync(st.d_state[st.cur] + 7, (size_t)sddc::kStereoStateWords * 4, 0, (size_t)4 * 4, (size_t)st.nch,
+                                 h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+    st.pos = pos;
+    return SDDC_OK;
+}
+
+// the checks both calls share (under h->mu)
+static int check_chst_args(const sddc_ddc_t *h, const void *in, int nch, size_t nsamp, size_t in_stride, const void *left,
+                           const void *right, size_t out_stride, const void *stereo, const void *count, const void *level,
+                           const void *phase)
+{
+    const ChannelStereo &st = h->chst;
+    if (st.modes.empty()) return fail(SDDC_ERR_STATE, "channel stereo decoder: no decoder set");
+    if (nch != st.nch)
+        return fail(SDDC_ERR_STATE, "channel stereo decoder: the decoder is set for %d channels, the call has %d", st.nch, nch);
+    if (nsamp == 0 || nsamp > ((size_t)1 << 40)) return fail(SDDC_ERR_ARG, "nsamp must be in 1..2^40 (got %zu)", nsamp);
+    if (!in || !left || !right) return fail(SDDC_ERR_ARG, "null input or output buffer");
+    if (nch > 1 && in_stride < nsamp) return fail(SDDC_ERR_ARG, "in_stride must be >= nsamp (got %zu, nsamp %zu)", in_stride, nsamp);
+    if (nch > 1 && out_stride < nsamp)
+        return fail(SDDC_ERR_ARG, "out_stride must be >= nsamp (got %zu, nsamp %zu)", out_stride, nsamp);
+    const uintptr_t is = st.in_fmt == SDDC_DDC_AUDIO_S16 ? 2 : 4, os = st.out_fmt == SDDC_DDC_AUDIO_S16 ? 2 : 4;
+    if (((uintptr_t)in & (is - 1)) != 0) return fail(SDDC_ERR_ARG, "the input must be %d-byte aligned", (int)is);
+    if ((((uintptr_t)left | (uintptr_t)right) & (os - 1)) != 0) return fail(SDDC_ERR_ARG, "the outputs must be %d-byte aligned", (int)os);
+    if ((((uintptr_t)stereo | (uintptr_t)count | (uintptr_t)level | (uintptr_t)phase) & 3) != 0)
+        return fail(SDDC_ERR_ARG, "the side outputs must be 4-byte aligned");
+    const uintptr_t ia = (uintptr_t)in, la = (uintptr_t)left, ra = (uintptr_t)right;
+    const uintptr_t ospan = ((uintptr_t)(nch - 1) * (nch > 1 ? out_stride : 0) + nsamp) * os;
+    const uintptr_t ib = ia + ((uintptr_t)(nch - 1) * (nch > 1 ? in_stride : 0) + nsamp) * is;
+    const uintptr_t lb = la + ospan, rb = ra + ospan;
+    if ((ia < lb && la < ib) || (ia < rb && ra < ib)) return fail(SDDC_ERR_ARG, "the input and an output overlap");
+    if (la < rb && ra < lb) return fail(SDDC_ERR_ARG, "the two outputs overlap");
+    return SDDC_OK;
+}
+
+// The call in launch sets of at most run_blocks blocks per channel (the scratch holds eight words per channel
+// and block of a set, and the kernels index a set with an int).
+static int chst_launch(sddc_ddc_t *h, const void *d_in, int nch, size_t nsamp, size_t in_stride, void *d_left, void *d_right,
+                       size_t out_stride, uint32_t *d_stereo, uint32_t *d_count, float *d_level, float *d_phase, hipStream_t s)
+{
+    ChannelStereo &st = h->chst;
+    const size_t B = SDDC_DDC_STEREO_BLOCK;
+    const size_t run_blocks = (size_t)(st.run_blocks > 0 ? st.run_blocks : ChannelStereo::kDefaultRunBlocks);
+    const size_t blocks = ((size_t)(st.pos % B) + nsamp + B - 1) / B;
+    const size_t need = sddc::kStereoScratchWords((size_t)nch, blocks < run_blocks ? blocks : run_blocks);
+    if (need > st.scratch_cap) {
+        HIP_TRY(st.readers.sync());   // an earlier launch may still use the scratch
+        if (int rc = grow_device_buffer(&st.d_scratch, &st.scratch_cap, need, "channel stereo decoder", "scratch words")) return rc;
+    }
+    HIP_TRY(st.readers.order_before(s));
+    const bool in16 = st.in_fmt == SDDC_DDC_AUDIO_S16, out16 = st.out_fmt == SDDC_DDC_AUDIO_S16;
+    const size_t is = in16 ? 2 : 4, os = out16 ? 2 : 4;
+    hipError_t e = hipSuccess;
+    for (size_t done = 0; done < nsamp && e == hipSuccess;) {
+        const size_t hs = (size_t)(st.pos % B);
+        size_t n = nsamp - done;
+        if (n > run_blocks * B - hs) n = run_blocks * B - hs;
+        e = sddc::launch_channel_stereo(h->tables, static_cast<const char *>(d_in) + done * is, in16, nch, n, in_stride, st.pos, st.word,
+                                        st.d_modes, st.d_thr, st.window, st.attack, st.hang, st.d_state[st.cur], st.d_state[st.cur ^ 1],
+                                        st.d_scratch, static_cast<char *>(d_left) + done * os, static_cast<char *>(d_right) + done * os,
+                                        out16, out_stride, d_stereo, d_count, d_level, d_phase, done > 0, st.max_wgs, h->device, s);
+        if (e != hipSuccess) break;
+        st.cur ^= 1;
+        st.pos += n;
+        done += n;
+    }
+    const hipError_t er = st.readers.record(s);   // whatever was enqueued stays ordered
+    HIP_TRY(e);
+    HIP_TRY(er);
+    return SDDC_OK;
+}
+
+int sddc_ddc_channel_stereo_device(sddc_ddc_t *h, const void *d_mpx, int nch, size_t nsamp, size_t in_stride, void *d_left,
+                                   void *d_right, size_t out_stride, uint32_t *d_stereo, uint32_t *d_count, float *d_level,
+                                   float *d_phase, void *hip_stream)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->cpu) return fail(SDDC_ERR_STATE, "channel_stereo_device: a CPU handle has no device path");
+    if (int rc = check_chst_args(h, d_mpx, nch, nsamp, in_stride, d_left, d_right, out_stride, d_stereo, d_count, d_level, d_phase))
+        return rc;
+    DeviceGuard g(h->device);
+    HIP_TRY(g.err);
+    return chst_launch(h, d_mpx, nch, nsamp, in_stride, d_left, d_right, out_stride, d_stereo, d_count, d_level, d_phase,
+                       (hipStream_t)hip_stream);
+}
+
+int sddc_ddc_channel_stereo_host(sddc_ddc_t *h, const void *mpx, int nch, size_t nsamp, size_t in_stride, void *left, void *right,
+                                 size_t out_stride, uint32_t *stereo, uint32_t *count, float *level, float *phase)
+{
+    if (!h) return fail(SDDC_ERR_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (int rc = check_chst_args(h, mpx, nch, nsamp, in_stride, left, right, out_stride, stereo, count, level, phase)) return rc;
+    ChannelStereo &st = h->chst;
+    const bool in16 = st.in_fmt == SDDC_DDC_AUDIO_S16, out16 = st.out_fmt == SDDC_DDC_AUDIO_S16;
+    if (h->cpu) {
+        sddc::cpu::R2iq::channel_stereo(mpx, in16, nch, nsamp, nch > 1 ? in_stride : 0, st.word, st.modes.data(), st.thr.data(),
+                                        st.window, st.attack, st.hang, st.pos, st.state_h.data(), left, right, out16,
+                                        nch > 1 ? out_stride : 0, stereo, count, level, phase);
+        st.pos += nsamp;
+        return SDDC_OK;
+    }
+    DeviceGuard g(h->device);
+    HIP_TRY(g.err);
+    // the spans that hold every channel's samples and outputs; the right streams follow the left ones
+    const size_t is = in16 ? 2 : 4, os = out16 ? 2 : 4;
+    const size_t in_bytes = ((size_t)(nch - 1) * (nch > 1 ? in_stride : 0) + nsamp) * is;
+    const size_t out_bytes = (((size_t)(nch - 1) * (nch > 1 ? out_stride : 0) + nsamp) * os + 15) / 16 * 16;
+    const size_t n = (size_t)nch;
+    if (int rc = grow_device_buffer(&st.d_in, &st.in_cap, in_bytes, "channel_stereo_host", "input bytes")) return rc;
+    if (int rc = grow_device_buffer(&st.d_out, &st.out_cap, 2 * out_bytes, "channel_stereo_host", "output bytes")) return rc;
+    if (int rc = grow_device_buffer(&st.d_side, &st.side_cap, n * 6, "channel_stereo_host", "side outputs")) return rc;
+    void *d_left = st.d_out, *d_right = static_cast<char *>(st.d_out) + out_bytes;
+    uint32_t *d_stereo = stereo ? st.d_side : nullptr, *d_count = count ? st.d_side + n : nullptr;
+    float *d_level = level ? reinterpret_cast<float *>(st.d_side + 2 * n) : nullptr;
+    float *d_phase = phase ? reinterpret_cast<float *>(st.d_side + 4 * n) : nullptr;
+    HIP_TRY(hipMemcpyAsync(st.d_in, mpx, in_bytes, hipMemcpyHostToDevice, h->stream));
+    const int rc = chst_launch(h, st.d_in, nch, nsamp, in_stride, d_left, d_right, out_stride, d_stereo, d_count, d_level, d_phase,
+                               h->stream);
+    if (rc == SDDC_OK) {   // the streams alone: the caller's memory between them stays as it is
+        const std::pair<void *, void *> outs[2] = {{left, d_left}, {right, d_right}};
+        for (const auto &o : outs) {
+            if (nch == 1 || out_stride == nsamp)
+                HIP_TRY(hipMemcpyAsync(o.first, o.second, ((size_t)(nch - 1) * (nch > 1 ? out_stride : 0) + nsamp) * os,
+                                       hipMemcpyDeviceToHost, h->stream));
+            else
+                HIP_TRY(hipMemcpy2DAsync(o.first, out_stride * os, o.second, out_stride * os, nsamp * os, n, hipMemcpyDeviceToHost,
+                                         h->stream));
+        }
+        if (stereo) HIP_TRY(hipMemcpyAsync(stereo, d_stereo, n * 4, hipMemcpyDeviceToHost, h->stream));
+        if (count) HIP_TRY(hipMemcpyAsync(count, d_count, n * 4, hipMemcpyDeviceToHost, h->stream));
+        if (level) HIP_TRY(hipMemcpyAsync(level, d_level, n * 8, hipMemcpyDeviceToHost, h->stream));
+        if (phase) HIP_TRY(hipMemcpyAsync(phase, d_phase, n * 8, hipMemcpyDeviceToHost, h->stream));
     }
     HIP_TRY(hipStreamSynchronize(h->stream));   // also after a failed launch: the caller's input is free again
     return rc;

@@ -145,7 +145,22 @@ extern "C" {
  * with a loop.  The grid changes no output bit (tests). */
 #define SDDC_DDC_PARAM_CHARS_MAX_WGS 30
 
+/* SDDC_DDC_PARAM_CHST_MAX_WGS = n > 0: each of the channel stereo decoder's grids is at most n workgroups, as
+ * param 25 for the tone detector; 0 (default): full residency with a loop.  The grid changes no output bit
+ * and no side output (tests). */
+#define SDDC_DDC_PARAM_CHST_MAX_WGS 31
+
+/* SDDC_DDC_PARAM_CHST_RUN_BLOCKS = n in 1..2^20: a call of the channel stereo decoder is cut into launch sets
+ * of at most n blocks per channel (the scratch holds eight words per channel and block of a set); 0: 4096.
+ * The run length changes no output bit and no side output (tests). */
+#define SDDC_DDC_PARAM_CHST_RUN_BLOCKS 32
+
 int sddc_ddc_internal_set_param(sddc_ddc_t *h, int param, int value);
+/* Move the channel stereo decoder's stream position to pos, a multiple of 256 W (SDDC_ERR_ARG otherwise;
+ * SDDC_ERR_STATE: no decoder set): the unfinished window's sums and the unfinished block are cleared, the gate,
+ * the phase and the last window's results are kept.  It lets tests start a stream next to the 2^32 wrap of the
+ * sample phase. */
+int sddc_ddc_internal_chst_set_position(sddc_ddc_t *h, uint64_t pos);
 /* Move the channel tone detector's stream position to pos, a multiple of 256 W (SDDC_ERR_ARG otherwise;
  * SDDC_ERR_STATE: no detector set): the unfinished window's sums and the unfinished block are cleared, the
  * gate and the last window's results are kept.  It lets tests start a stream next to the 2^32 wrap of the

@@ -241,6 +241,15 @@ def dcs_window(fs: float, bitrate: float = 134.4):
     return int(w.value), int(b.value)
 
 
+STEREO_BLOCK = 256                        # SDDC_DDC_STEREO_BLOCK: the stereo decoder's block length B
+STEREO_MONO, STEREO_AUTO = 0, 1           # SDDC_DDC_STEREO_MONO (both outputs are the input), _AUTO
+
+
+def stereo_pilot_word(fs: float) -> int:
+    """The phase word of the 19 kHz stereo pilot at the MPX rate fs: round(19000 / fs * 2^32) (sddc_ddc_bfo_word)."""
+    return bfo_word(19000.0 / fs)
+
+
 def psd_to_dbfs(psd) -> np.ndarray:
     """R2iq.spectrum's output in dB relative to a full-scale real tone (amplitude 32768 reads
     32768^2 / 4 at its bin centre): 10 log10(4 psd / 32768^2); -inf where psd is 0."""
@@ -277,6 +286,7 @@ class R2iq:
         self._squelch = None  # (nch, sense, in_format, out_format) of setChannelSquelch
         self._tone = None     # (nch, ntones, sense_format, in_format, out_format) of setChannelToneDetector
         self._dcs = None      # (nch, sense_format, in_format, out_format) of setChannelDcsDecoder
+        self._stereo = None   # (nch, in_format, out_format) of setChannelStereoDecoder
 
     # -- lifecycle --------------------------------------------------------
     @property
@@ -1376,6 +1386,95 @@ class R2iq:
                                                   None if d_out is None else d_out.data_ptr(), out_stride,
                                                   *(None if t is None else t.data_ptr() for _, t, _, _ in sides),
                                                   _stream_handle(stream)))
+
+    # -- channel stereo decoder ------------------------------------------------------
+    def setChannelStereoDecoder(self, pilot_word: int, modes, params, window: int = 8, attack: int = 1, hang: int = 0,
+                                fmt_in: int = AUDIO_F32, fmt_out: int = AUDIO_F32) -> None:
+        """The streaming WFM stereo decoder of channel_stereo / channel_stereo_device: pilot_word is the 19 kHz
+        pilot's phase word (stereo_pilot_word); modes uint8 [nch], STEREO_MONO (both outputs are the input) or
+        STEREO_AUTO; params float32 [nch, 4] = (rho_open, rho_close, e_min, g): the share of a window's energy in
+        the pilot that opens and that keeps open (0 < rho_close <= rho_open <= 1; 0.004 and 0.002 are the starting
+        point), the mean square per sample below which a window is silence, and the separation gain (1).  window:
+        1..256 blocks of 256 samples (8 at 250 kS/s); attack: 1..255 windows before a channel turns stereo; hang:
+        0..65535 windows it stays stereo without the pilot; fmt_*: AUDIO_F32 or AUDIO_S16 of the MPX and of the two
+        outputs.  Every call starts a new stream.  modes=None turns the stage off."""
+        if modes is None or np.size(modes) == 0:
+            check(self._L.sddc_ddc_set_channel_stereo_decoder(self._h, 0, None, None, 0, 0, 0, 0, 0, 0))
+            self._stereo = None
+            return
+        m = np.ascontiguousarray(np.asarray(modes, np.uint8).reshape(-1))
+        p = np.ascontiguousarray(np.asarray(params, np.float32))
+        if p.ndim != 2 or p.shape != (m.shape[0], 4):
+            raise DDCError(-1, "params must be [nch, 4] with one row per mode")
+        check(self._L.sddc_ddc_set_channel_stereo_decoder(self._h, int(pilot_word) & 0xffffffff, m.ctypes.data, p.ctypes.data,
+                                                          m.shape[0], int(window), int(attack), int(hang), int(fmt_in),
+                                                          int(fmt_out)))
+        self._stereo = (m.shape[0], int(fmt_in), int(fmt_out))
+
+    def resetChannelStereoDecoder(self) -> None:
+        """A new stream: every channel mono, q = (1, 0), the position 0."""
+        check(self._L.sddc_ddc_channel_stereo_reset(self._h))
+
+    def channel_stereo(self, mpx: np.ndarray):
+        """The stereo decoder on host arrays: mpx is float32 (AUDIO_S16 input: int16) [nch, nsamp], any nsamp >= 1; a
+        single stream may drop the channel axis.  Returns a dict: left, right (float32 / int16 [nch, nsamp]),
+        stereo (uint32 [nch], the gate for the next window), count (uint32 [nch], this call's samples written in
+        stereo), level (float32 [nch, 2] = P, E of the last completed window), phase (float32 [nch, 2] = (qr, qi) in
+        force).  Keeps every channel's state for the next call."""
+        if self._stereo is None:
+            raise DDCError(-4, "no channel stereo decoder set")
+        nch, fin, fout = self._stereo
+        x = np.asarray(mpx, np.int16 if fin == AUDIO_S16 else np.float32)
+        if x.ndim == 1:
+            x = x[None, :]
+        x = np.ascontiguousarray(x)
+        if x.ndim != 2 or x.shape[1] < 1:
+            raise DDCError(-1, "mpx must be [nch, nsamp] with nsamp >= 1")
+        n, nsamp = x.shape
+        left, right = (np.empty((n, nsamp), np.int16 if fout == AUDIO_S16 else np.float32) for _ in range(2))
+        st = np.empty(n, np.uint32)
+        c = np.empty(n, np.uint32)
+        lv = np.empty((n, 2), np.float32)
+        ph = np.empty((n, 2), np.float32)
+        check(self._L.sddc_ddc_channel_stereo_host(self._h, x.ctypes.data, n, nsamp, nsamp, left.ctypes.data, right.ctypes.data,
+                                                   nsamp, st.ctypes.data, c.ctypes.data, lv.ctypes.data, ph.ctypes.data))
+        return {"left": left, "right": right, "stereo": st, "count": c, "level": lv, "phase": ph}
+
+    def channel_stereo_device(self, d_mpx, nch: int, nsamp: int, in_stride: int, d_left, d_right, out_stride: int,
+                              d_stereo=None, d_count=None, d_level=None, d_phase=None, stream=None) -> None:
+        """The stereo decoder on device buffers: d_mpx is a float32 (AUDIO_S16 input: int16) device tensor, the
+        FM demodulator's audio buffer, channel c's nsamp samples at c * in_stride; d_left and d_right take channel
+        c's outputs at c * out_stride and overlap neither the input nor each other (two views of one tensor, the
+        right one nch * out_stride after the left one, make 2 nch streams for one audio resampler call).  d_stereo,
+        d_count: None or int32 device tensors of nch values; d_level, d_phase: None or float32 [nch, 2].  Enqueued on
+        `stream` like process_device; the calls of one handle run in call order."""
+        import torch
+        if self._stereo is None:
+            raise DDCError(-4, "no channel stereo decoder set")
+        _, fin, fout = self._stereo
+        if nch < 1 or nsamp < 1:
+            raise DDCError(-1, "nch and nsamp must be >= 1")
+        sides = (("d_stereo", d_stereo, torch.int32, nch), ("d_count", d_count, torch.int32, nch),
+                 ("d_level", d_level, torch.float32, 2 * nch), ("d_phase", d_phase, torch.float32, 2 * nch))
+        if not all(t is not None and t.is_cuda for t in (d_mpx, d_left, d_right)) or \
+                not all(t is None or t.is_cuda for _, t, _, _ in sides):
+            raise DDCError(-1, "device path needs device tensors")
+        odt = torch.int16 if fout == AUDIO_S16 else torch.float32
+        bufs = (("d_mpx", d_mpx, in_stride, torch.int16 if fin == AUDIO_S16 else torch.float32),
+                ("d_left", d_left, out_stride, odt), ("d_right", d_right, out_stride, odt))
+        for name, t, stride, dt in bufs:
+            if t.dtype != dt or not t.is_contiguous():
+                raise DDCError(-1, f"{name} must be a contiguous {dt} tensor")
+            need = (nch - 1) * stride + nsamp
+            if t.numel() < need:
+                raise DDCError(-1, f"{name} has {t.numel()} samples, need {need}")
+        for name, t, dt, cnt in sides:
+            if t is not None and (t.dtype != dt or not t.is_contiguous() or t.numel() < cnt):
+                raise DDCError(-1, f"{name} must be a contiguous {dt} tensor of at least {cnt} values")
+        check(self._L.sddc_ddc_channel_stereo_device(self._h, d_mpx.data_ptr(), nch, nsamp, in_stride, d_left.data_ptr(),
+                                                     d_right.data_ptr(), out_stride,
+                                                     *(None if t is None else t.data_ptr() for _, t, _, _ in sides),
+                                                     _stream_handle(stream)))
 
 
 def _check_device_buffers(d_in, nblk, d_out, out_floats, fmt=0):

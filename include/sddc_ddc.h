@@ -1084,6 +1084,98 @@ int sddc_ddc_channel_dcs_host(sddc_ddc_t *h, const void *sense, size_t sense_str
                               size_t in_stride, void *out, size_t out_stride, int32_t *code, uint32_t *open, uint32_t *count,
                               uint32_t *info);
 
+/* ---- channel stereo decoder: streaming WFM stereo from the MPX -----------------------------------
+ * The FM discriminator output of a broadcast station (192 or 250 kS/s) is the stereo multiplex (MPX): L + R up
+ * to 15 kHz, a pilot at 19 kHz, and L - R double-sideband around a suppressed carrier at 38 kHz whose phase is
+ * twice the pilot's.  This stage measures the pilot per channel (the tone detector's single-bin DFT over
+ * windows of 256-sample blocks), decides stereo or mono with the squelch's gate, rebuilds the carrier from the
+ * exact 32-bit phase word and the measured pilot phase, and writes L = x + d and R = x - d, d = 2 g x sin(2 psi),
+ * at the MPX rate.  Matrixing commutes with the low-pass, so the existing stages finish the job unchanged: the
+ * audio resampler (15 kHz low-pass, 24/125 from 250 kS/s) on the 2 nch output streams, then the audio filter
+ * (de-emphasis, a 19 kHz notch where the resampler's stop band is not enough).  d_left and d_right are
+ * separate pointers; a caller who passes d_right = d_left + nch * out_stride gets 2 nch streams of the stride
+ * out_stride that one audio resampler call of a second handle takes.
+ * What it is NOT: it does not track a pilot frequency offset (the carrier runs at exactly twice the set
+ * word, the measured phase is constant over a window and applied to the next one, so an offset of df turns
+ * the carrier by 2 pi df 256 W / fs per window: W is the trade between the noise on the phase and this
+ * error); no de-emphasis, no 15 kHz low-pass and no pilot notch (the audio resampler and the audio filter);
+ * no RDS; no blend by signal quality: a window is stereo or it is mono.
+ *
+ * The definition (normative; csrc/stereo_math.h holds the operations, shared by both backends, float,
+ * contraction off, only *, +, -, explicit fmaf, one sqrt, correctly rounded /, comparisons, selects and
+ * integers; the tone detector's, the blanker's, the demodulator's and the squelch's functions are used, not
+ * restated).  B = SDDC_DDC_STEREO_BLOCK = 256; p >= 0 is the stream index since the last set or reset, k = p
+ * div B its block, j = k div W its window.
+ *   Per handle.  The pilot's phase word w in 2^-32 cycles per sample, sddc_ddc_bfo_word(19000 / fs), not 0; w2
+ *                = 2 w mod 2^32; a window of W blocks (1..256); an attack of A windows (1..255); a hang of H
+ *                windows (0..65535); the formats of the input and of the two outputs.
+ *   Per channel. A mode: SDDC_DDC_STEREO_MONO (bypass: both outputs are the input; the pilot is still
+ *                measured) or SDDC_DDC_STEREO_AUTO; rho_open >= rho_close, both in (0, 1], the share of the
+ *                window's energy in the pilot that opens and that keeps open; e_min >= 0, a mean square per
+ *                sample below which a window counts as silence; the separation gain g >= 0 (1 for a
+ *                discriminator of flat response; above 1 makes up for the roll-off at 38 kHz).  Scaled once at
+ *                set time: To = (float)((double)rho_open * 256 W), Tc and Emin likewise, g2 = 2 g.
+ *   Sample.      x, SDDC_DDC_AUDIO_F32 or _S16 (read as (float)v).  q = x * x; a sample with !(q <= FLT_MAX)
+ *                enters the sums as x = 0, q = 0 and marks its window bad (the tone detector's rule).
+ *   Block, window.  Re_k, Im_k, p_k and the folds Zr, Zi, E: the tone detector's, for the single tone w.  P =
+ *                (Zr * Zr) + (Zi * Zi); u = !bad && E > Emin && P > To * E; v the same with Tc.  (P, E) are the
+ *                tone detector's d_level for the table {w} and the same W on the same stream, bit for bit.
+ *   Pilot phase. For x_i = sin(phi_i + alpha) the sum Z = sum x_i e^{j phi_i} is (N / 2) (sin alpha + j cos
+ *                alpha).  Where v_j holds: n = sqrtf(P), vr = Zi / n, vi = Zr / n, qr = fmaf(vr, vr, -(vi * vi)),
+ *                qi = (2 * vr) * vi; otherwise q_j = q_{j-1}.  A new stream has q = (1, 0).
+ *   Gate.        The squelch's state machine, once per completed window, as in the tone detector.  The gate and
+ *                the q after window j apply to window j + 1: no look-ahead and no delay.
+ *   Carrier.     Block k of an open window, sample i of the block: (tc_i, ts_i) = sincos_word(w2 * i); (rc, rs)
+ *                = sincos_word(w2 * (uint32)(256 k)); rr = fmaf(qr, rc, -(qi * rs)), ri = fmaf(qr, rs, qi * rc);
+ *                sub_i = fmaf(tc_i, ri, ts_i * rr): sin(2 psi) for a pilot sin(psi), the BS.450 relation.
+ *   Outputs.     Open window of an AUTO channel: d = (g2 * x) * sub, L = x + d, R = x - d; S16 outputs by the
+ *                demodulator's conversion.  Closed window or MONO channel: L = R = the input sample as it is
+ *                (the tone detector's pass rule: a NaN payload survives F32 to F32, S16 to F32 is (float)v).
+ *   Side outputs, each NULL or per channel: stereo (uint32): the gate for the next window (MONO: 0); count
+ *                (uint32, modulo 2^32): the samples this call wrote in stereo; level ([nch][2] float): P and E
+ *                of the last completed window, the figures to calibrate rho (P / (256 W E)) and e_min (E /
+ *                (256 W)) from; phase ([nch][2] float): (qr, qi) in force.  Before any window completes: 0, 0,
+ *                zeros, (1, 0).
+ * Outputs and side outputs are bit-identical from run to run, for any grid, run length and cut of a stream
+ * into calls, for a channel alone or among others, and between a GPU handle and a CPU handle, for samples
+ * that are 0 or of magnitude in [2^-40, 2^40] and g 0 or in [2^-40, 2^40] (stereo_math.h shows why nothing that
+ * decides depends on a subnormal or an overflow: P > Tc * E > 0 excludes P = 0, n is in (2^-50, 2^60), |vr|,
+ * |vi| <= 1 + 3.02 u).  Against a float64 evaluation of the same definition (derived in stereo_math.h; u =
+ * 2^-24, X the sum of |x| over the window, r = sqrt(2) (38 + W) u X / sqrt(P64), dv = r / (1 - r / 2) + 3.02 u):
+ * |qr - qr64|, |qi - qi64| <= dv (2 + dv) + 2.02 u, and given the same float32 q: |L - L64|, |R - R64| <= 1.01 u
+ * (|x| + 22 |g2 x|).  The decisions differ only inside the tone detector's bounds.
+ * State per handle, on the device for a GPU handle, independent of every other stage's: the position; per
+ * channel the gate, q, the last completed window's P and E, the unfinished window's sums and bad flag, and
+ * the unfinished block's samples. */
+#define SDDC_DDC_STEREO_BLOCK 256
+#define SDDC_DDC_STEREO_MAX_WINDOW 256
+#define SDDC_DDC_STEREO_MONO 0
+#define SDDC_DDC_STEREO_AUTO 1
+/* modes: host array [nch]; params: host array [nch][4] = (rho_open, rho_close, e_min, g); 1 <= nch <=
+ * SDDC_DDC_MAX_CHANNELS; window, attack, hang with the tone detector's limits; the formats
+ * SDDC_DDC_AUDIO_F32 or _S16.  A violation returns SDDC_ERR_ARG and sets nothing.  modes or params NULL or nch
+ * == 0 turns the stage off and frees its state.  Every set call starts a new stream (state and position), and
+ * waits for the stage's launches in flight. */
+int sddc_ddc_set_channel_stereo_decoder(sddc_ddc_t *h, uint32_t pilot_word, const uint8_t *modes, const float *params, int nch,
+                                        int window, int attack, int hang, int in_format, int out_format);
+/* a new stream: state and position (SDDC_ERR_STATE: no decoder set) */
+int sddc_ddc_channel_stereo_reset(sddc_ddc_t *h);
+/* GPU handles; enqueued on hip_stream, returns after launch.  Channel c's nsamp MPX samples at d_mpx + c *
+ * in_stride samples, its outputs at d_left + c * out_stride and d_right + c * out_stride; strides >= nsamp for
+ * nch > 1; bases aligned to a sample; any 1 <= nsamp <= 2^40.  The outputs overlap neither the input nor each
+ * other; nothing is written between the streams or outside them.  d_stereo, d_count: NULL or nch device
+ * entries; d_level, d_phase: NULL or [nch][2].  SDDC_ERR_STATE: no decoder set, another nch than the set one, a
+ * CPU handle.  SDDC_ERR_ARG: the rest.  A failed call changes no state.  The calls of one handle share the
+ * state and the position: they run one after the other in call order, whatever their streams. */
+int sddc_ddc_channel_stereo_device(sddc_ddc_t *h, const void *d_mpx, int nch, size_t nsamp, size_t in_stride, void *d_left,
+                                   void *d_right, size_t out_stride, uint32_t *d_stereo, uint32_t *d_count, float *d_level,
+                                   float *d_phase, void *hip_stream);
+/* Host buffers, the same layouts.  GPU handle: copy in, kernels, copy back, synchronous; it advances the
+ * same device state as the device call.  CPU handle: the definition's loop through the same arithmetic
+ * header. */
+int sddc_ddc_channel_stereo_host(sddc_ddc_t *h, const void *mpx, int nch, size_t nsamp, size_t in_stride, void *left, void *right,
+                                 size_t out_stride, uint32_t *stereo, uint32_t *count, float *level, float *phase);
+
 /* ---- ingest ---------------------------------------
  * Pin a caller-owned host region (hipHostRegister) so the host path DMAs blocks
  * from it and output into it directly instead of staging through the library's
